@@ -11,9 +11,14 @@ over N GPUs of one node (one process per GPU, RCCL gradient all-reduce overlappe
     python bench.py --gpus 8 --shard-optimizer                 (reduce-scatter / 1/N update / all-gather instead of all-reduce + replicated update)
     python bench.py --multiscale [--gpus 4]                    (BASELINE configs[3]: a different input size every step)
 
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR    (the last timed step's loss and updated variables as DIR/*.npy)
+    python bench.py --full                                     (the headline line plus every object listed below)
+
 A "step" = per-image standardisation -> forward (batch-stat BN) -> YOLOv2 loss fwd+bwd -> backward
 -> gradient all-reduce (N>1) -> Adam, on a synthetic batch that is already resident in HBM.
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+Rank 0 prints ONE JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds per timed step, ...).
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs if asked and prints the line; with --full it
+also measures, after the timed region (each --no-* switch drops one):
   roofline      the dominant kernel: the 24 3x3 forward + data-gradient launches with > 64 filters (conv3x3_pp_kernel on images up to
                 55 wide, conv_igemm_kernel<bf16,128,...,KS=3> on the 104x104 stage) -- algorithmic FLOPs / RAW HIP-event time of
                 those launches in instrumented steps right after the timed region, against the 2.5 PFLOP/s dense bf16 MFMA
@@ -25,6 +30,7 @@ Rank 0 prints ONE JSON line (contract in the task statement) with two extra obje
                 fraction of the 157.3 TFLOP/s f32 matrix peak
   detect        BASELINE configs[4]: batch-256 detect p50/p99 with (a) the network's own scores, (b) the sparse and
                 (c) the dense NMS stress inputs of BASELINE.md section 2 written over the decoded boxes
+  comm          N > 1: per-bucket collective and exposed time from three instrumented steps
 """
 import argparse
 import json
@@ -262,10 +268,34 @@ def _lib_env_overrides():
     return _lib.env_overrides()
 
 
+DUMP_SAMPLE = 4 << 20       # values of the variables written by --dump-outputs (16 MB of f32)
+
+
+def dump_outputs(outdir, sess):
+    """--dump-outputs: what the last timed step computed, as a caller of TrainSession.step receives it -- the loss and its four
+    objectives (fetch()) and the updated variables (filters, biases, BN scales and moving statistics, flattened in graph order;
+    a fixed seeded sample of DUMP_SAMPLE of their ~51 M values).  About 16 MB in all.  Two runs of one build differ as well: the
+    gradient sums use atomics, and Adam turns order-of-summation noise into update-sized steps (measured over 25 steps at
+    batch 16: total_loss 1e-3 relative, variables 2e-4 relative L2, at most 1.1e-4 absolute)."""
+    from yolo_tf_amd.model.yolo2 import OBJECTIVE_KEYS
+    os.makedirs(outdir, exist_ok=True)
+    got = sess.fetch()
+    e = sess.engine
+    flat = torch.cat([e.var[v.name].reshape(-1) for v in e.graph.variables.values()])
+    n = flat.numel()
+    idx = np.unique(np.random.RandomState(0).randint(0, n, DUMP_SAMPLE)) if n > DUMP_SAMPLE else np.arange(n)
+    sample = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+    arrays = {'total_loss': np.array([got['total_loss']], np.float64),
+              'objectives': np.array([got[k] for k in OBJECTIVE_KEYS], np.float64),
+              'variables_sample': sample.astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=100, help='timed steps (0.4 s of GPU time at the default: long enough for the clocks to settle; 20 / 100 / 300 steps measure the same rate within 1 %)')
+    ap.add_argument('--steps', type=int, default=100, help='timed steps (0.4 s of GPU time at the default: long enough for the clocks to settle; 20 / 100 / 300 steps measure the same rate within 1 %%)')
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--batch', type=int, default=16, help='images per GPU (weak scaling)')
     ap.add_argument('--global-batch', type=int, default=0, help='fixed total batch split over the GPUs (strong scaling; BASELINE configs[2] = 64 on 8)')
@@ -280,6 +310,10 @@ def main():
     ap.add_argument('--backend', default=None, choices=['nccl', 'gloo'], help='process-group backend for N > 1 (default nccl = RCCL; gloo lets the tests run two ranks on one GPU)')
     ap.add_argument('--no-f32', action='store_true', help='skip the f32 parity-mode sub-object (10 steps of the same workload in exact-f32 arithmetic, rank 0, N = 1)')
     ap.add_argument('--no-detect', action='store_true', help='skip the batch-256 detect p50/p99 report (BASELINE configs[4]) on rank 0')
+    ap.add_argument('--full', action='store_true', help='after the timed region also measure the roofline pass, the CPU baselines, the f32 parity mode, '
+                                                        'batch-256 detect and (N > 1) the per-bucket communication report; the --no-* switches drop single ones')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the last timed step\'s loss, objectives and a seeded sample of '
+                                                                         'the updated variables as DIR/<name>.npy (rank 0)')
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -322,7 +356,7 @@ def main():
     gen = torch.Generator(device='cuda').manual_seed(1234 + rank)
     images = torch.rand(args.batch, args.size, args.size, 3, device='cuda', generator=gen) * 255.0
     sess.upload_labels(data.synthetic_batch(args.batch, args.names, cells, cells, seed=4321 + rank))
-    timer = None if args.no_kernel_timer else KernelTimer()
+    timer = KernelTimer() if args.full and not args.no_kernel_timer else None
     sess.engine.kernel_timer = timer
 
     def barrier():
@@ -340,6 +374,8 @@ def main():
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sess)
     # Roofline pass, right after the timed region on the same session: the same training steps with HIP events around
     # every launch of the dominant kernel.  Kept out of the timed region because a timed event is a barrier packet:
     # ~35 of them per step stop back-to-back dispatch and cost 11 % of the step (measured), which would understate
@@ -362,6 +398,7 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device='cuda')
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if world > 1 and args.full:
         # per-bucket collective and EXPOSED time (how long the optimizer's stream waited for each bucket), from a few instrumented steps
         # after the timed region: makes the first multi-GPU run diagnosable (which bucket is not hidden behind backward / the update)
         sess.reducer.timing = True
@@ -421,11 +458,11 @@ def main():
                                                 '(events inside it cost 11 %% of the step)' % min(args.steps, 10),
                                'forward_launches_tflops': kf['tflops'] if kf else None, 'data_gradient_launches_tflops': kd['tflops'] if kd else None,
                                'one_by_one_launches_same_template': {'tflops': k1['tflops'], 'launches': k1['launches'], 'avg_launch_ms': k1['avg_ms']} if k1 else None}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(args.names, args.size)
-        if world == 1 and not args.no_f32 and args.dtype == 'bf16':
+        if world == 1 and args.full and not args.no_f32 and args.dtype == 'bf16':
             out['f32_parity_mode'] = f32_parity_mode(args)
-        if world == 1 and not args.no_detect:
+        if world == 1 and args.full and not args.no_detect:
             del sess
             torch.cuda.empty_cache()
             out['detect'] = detect_latency(args, basedir)
@@ -471,11 +508,14 @@ def multiscale(args, rank, world, basedir, dist):
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sess)
     comm_report = None
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device='cuda')
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if world > 1 and args.full:
         # per-bucket collective and EXPOSED time (how long the optimizer's stream waited for each bucket), from a few instrumented steps
         # after the timed region: makes the first multi-GPU run diagnosable (which bucket is not hidden behind backward / the update)
         sess.reducer.timing = True

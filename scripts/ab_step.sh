@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}; cd $R
 N=$1; shift
 for i in $(seq 1 $N); do for cfg in "$@"; do
   name=${cfg%%=*}; envs=${cfg#*=}
-  env $envs python bench.py --steps 80 --warmup 10 --no-cpu-baseline --no-detect --no-f32 2>/dev/null | python -c "
+  env $envs python bench.py --full --steps 80 --warmup 10 --no-cpu-baseline --no-detect --no-f32 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

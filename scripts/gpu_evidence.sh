@@ -3,7 +3,7 @@
 #   /usr/local/graft/bin/gpurun --timeout 1800 -- 'bash scripts/gpu_evidence.sh r05 bench trace traffic pmc layers wgrad configs tests'
 # Every section runs on the box of THIS call, writes gpurun_out/<tag>_<section>.* with the box id and commit in its first lines (copy what is to be
 # judged into profiles/), and is bounded by its own timeout.  Sections:
-#   bench    python bench.py (the driver's line: roofline, cpu_baseline, f32_parity_mode, detect)
+#   bench    python bench.py --full (the line with roofline, cpu_baseline, f32_parity_mode, detect), written under $BENCH_OUT (default bench_out/)
 #   trace    rocprofv3 --kernel-trace --stats of bench.py: product configuration + single stream, per-launch listing of the last step
 #   traffic  the same + FETCH_SIZE / WRITE_SIZE in separate PMC passes; refreshes the dominant kernel's bytes per launch
 #   pmc      SQ counters of forward + filter-gradient launches of six layers (scripts/one_layer.py), MFMA-busy calibrated on a pure MFMA loop
@@ -13,6 +13,7 @@
 #   tests    the whole -m gpu suite with durations
 #   rounds   same-box A/B of this tree's library against the previous round's (PREV=r05: profiles/baseline/libyolo2hip_r05.so), alternating
 R=${GRAFT_REPO_ROOT:-$PWD}; cd $R; mkdir -p gpurun_out; TAG=${1:-ev}; shift
+BENCH_OUT=${BENCH_OUT:-$R/bench_out}
 make -C oracle >/dev/null 2>&1
 BOX="box: hostname $(hostname), GPU $(/opt/rocm/bin/rocm-smi --showuniqueid 2>/dev/null | grep -i 'unique id: ' | head -1 | sed 's/.*Unique ID: *//'); commit $(cat .evidence_commit 2>/dev/null || echo '(snapshot)'); scripts/gpu_evidence.sh $TAG $* (ONE gpurun call)"
 echo "# $BOX" | tee gpurun_out/${TAG}_box.txt
@@ -20,9 +21,9 @@ hdr() { echo "# $1"; echo "# $BOX"; echo; }
 for sec in "$@"; do
   case $sec in
     bench)
-      ( time timeout 600 python bench.py ) > gpurun_out/${TAG}_bench.log 2>&1
-      { hdr "python bench.py (defaults: N = 1, 100 steps, 10 warm-up)"; grep '^{' gpurun_out/${TAG}_bench.log | tail -1; grep -E '^real' gpurun_out/${TAG}_bench.log; } > gpurun_out/${TAG}_bench_line.txt
-      grep '^{' gpurun_out/${TAG}_bench.log | tail -1 | cut -c1-400 ;;
+      mkdir -p $BENCH_OUT; ( time timeout 600 python bench.py --full ) > $BENCH_OUT/${TAG}_bench.log 2>&1
+      { hdr "python bench.py --full (N = 1, 100 steps, 10 warm-up)"; grep '^{' $BENCH_OUT/${TAG}_bench.log | tail -1; grep -E '^real' $BENCH_OUT/${TAG}_bench.log; } > $BENCH_OUT/${TAG}_bench_line.txt
+      grep '^{' $BENCH_OUT/${TAG}_bench.log | tail -1 | cut -c1-400 ;;
     trace|traffic)
       bash scripts/gpu_traffic.sh $([ $sec = trace ] && echo notraffic) > gpurun_out/${TAG}_traffic.log 2>&1
       for f in prof_summary.md prof1s_summary.md prof1s_last_step.txt prof_roofline.txt traffic_summary.md; do
@@ -49,7 +50,7 @@ for sec in "$@"; do
         if [ ! -f $OLD ]; then echo "no $OLD (bash scripts/build_baseline.sh $PREV <commit>)"; else
         for i in 1 2 3; do for which in old new; do
           if [ $which = old ]; then export YOLO2_LIB_PATH=$OLD YOLO2_LIB_BASELINE=1; else unset YOLO2_LIB_PATH YOLO2_LIB_BASELINE; fi
-          timeout 300 python bench.py --steps 60 --warmup 10 --no-cpu-baseline --no-detect --no-f32 2>/dev/null | python -c "
+          timeout 300 python bench.py --full --steps 60 --warmup 10 --no-cpu-baseline --no-detect --no-f32 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Final-state profiles: kernel trace (product config + single-stream), then HBM traffic counters in separate PMC passes.
 R=${GRAFT_REPO_ROOT:-$PWD}; mkdir -p $R/gpurun_out; cd /tmp; export TMPDIR=/tmp
-B="python $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-detect --no-f32"
+B="python $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-detect --no-f32"
 rm -rf $R/gpurun_out/prof $R/gpurun_out/prof1s $R/gpurun_out/pmc_fetch $R/gpurun_out/pmc_write
 timeout 600 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof -o run -- $B > $R/gpurun_out/prof.log 2>&1
 grep '"metric"' $R/gpurun_out/prof.log | cut -c1-200
