@@ -106,6 +106,29 @@ int yolo2_conv2d_wgrad(const void *X, const void *dY, float *dW,
                        int B, int H, int W, int Cin, int ldx, int Cout, int ldy, int ksize,
                        int dtype, void *stream);
 
+/* Workspace form of the same filter gradient (tf.gradients of conv2d, train.py:127-129; call sites model/yolo2/inference.py:37-48,73-118): the
+ * deterministic training mode.  Where yolo2_conv2d_wgrad splits the pixel reduction over several workgroups and lets them meet in f32 atomics, here
+ * every partial result goes with plain stores into a slot of its own in `ws` (slot r = pixel range r of the per-tap and the row-of-taps kernels, workgroup r
+ * of conv1's kernel and of the image layer's; slot layout = the layout of dW, HWIO) and a second launch on the same stream, wgrad_reduce_kernel, overwrites
+ * dW with the sum of the slots in an order that depends on the number of slots alone.
+ * Bytes of workspace for a shape: slots x slot_floats x 4 with slot_floats = k*k*Cin*Cout rounded up to a multiple of 4 (16-byte slots);
+ * 0 = the plan is a single range (yolo2_conv2d_wgrad stores already), and for arguments yolo2_conv2d_wgrad_ws would refuse.  Pure host query, no launch.
+ * workspace_bytes > 0 exactly when yolo2_conv2d_wgrad_accumulates() == 1 (both read one plan function); the one exception is the scalar-gather test
+ * hook, yolo2_debug_set_wgrad_variant(1), under which accumulates answers 1 for every shape to be safe. */
+size_t yolo2_conv2d_wgrad_workspace_bytes(int B, int H, int W, int Cin, int ldx, int Cout, int ldy, int ksize, int dtype);
+/* Same result contract as yolo2_conv2d_wgrad, except: dW is OVERWRITTEN for every shape (it may hold anything on entry, and so may ws), the value is a
+ * pure function of (X, dY, shape, compute-unit count of the device) -- bitwise equal from call to call, buffer to buffer, process to process --, and
+ * no float atomic is issued.  ws: 16-byte aligned; may be NULL when the query returns 0.  ws_bytes below the query's answer: YOLO2_E_ARG, nothing
+ * launched.  The tiles, ranges and block placement are those of yolo2_conv2d_wgrad (one plan function serves both and the plan queries). */
+int yolo2_conv2d_wgrad_ws(const void *X, const void *dY, float *dW, float *ws, size_t ws_bytes, int B, int H, int W,
+                          int Cin, int ldx, int Cout, int ldy, int ksize, int dtype, void *stream);
+/* Deterministic mode of the CALLING THREAD (default 0), for the entry points whose launch rule or reduction would otherwise sum floats in arrival
+ * order: with it on, yolo2_conv2d_ws / _bias_leaky never take the K-sliced form (f32 atomics into the partial image; stream-K or the unsplit grid run
+ * instead).  Results stay within the same bounds; they become a pure function of the inputs.  A deterministic engine switches it on for the
+ * duration of its own sweeps and off again, so it can share a process (and a thread) with default engines and direct callers. */
+int yolo2_set_deterministic(int on);
+int yolo2_get_deterministic(void);
+
 /* HWIO f32 master weights [k,k,Cin,Cout] -> the two K-contiguous operand layouts:
  *   Ffwd [Cout][k*k*ldcin]  : Ffwd[n][koff(r*k+s, c, ldcin)]  = W[r,s,c,n]
  *   Fdgr [Cin ][k*k*ldcout] : Fdgr[c][koff(r*k+s, n, ldcout)] = W[k-1-r,k-1-s,c,n]
@@ -429,6 +452,11 @@ int yolo2_bn_fold(const float *W, const float *gamma, const float *beta, const f
  * seg_off int64[nseg+1] element offsets into g; ws >= nseg doubles */
 int yolo2_clip_by_norm(float *g, const long *seg_off, int nseg, float clip, double *ws,
                        void *stream);
+/* the same clip (tf.clip_by_norm, train.py:127-129) with every tensor's sum of squares formed in a fixed order, for the deterministic training mode: 64
+ * workgroups per tensor store one partial each (no atomic), the scale pass adds them in index order.  ws: yolo2_clip_fixed_workspace_bytes(nseg) bytes
+ * (64 doubles per tensor), may hold anything on entry; a smaller ws_bytes: YOLO2_E_ARG, nothing launched. */
+size_t yolo2_clip_fixed_workspace_bytes(int nseg);
+int yolo2_clip_by_norm_fixed(float *g, const long *seg_off, int nseg, float clip, double *ws, size_t ws_bytes, void *stream);
 
 /* ---- diagnostics -----------------------------------------------------------------------------
  * fills out[64*4] with the raw result of ds_read_b64_tr_b16 over a 0..N ramp (layout self-test) */
@@ -469,6 +497,11 @@ void yolo2_debug_set_wgrad_variant(int variant);
 /* host-side plan of the row-of-taps filter-gradient kernel for a shape on a device with `cus` compute units (force_variant < 0: by rule):
  * out9 = {variant (-1: not taken), pixel ranges, padded pixels per range, workgroups, XCD mapping, plain stores, channel tile, filter tile, waves} */
 int yolo2_debug_wgrad_row_plan(int B, int H, int W, int Cin, int Cout, int cus, int force_variant, int *out9);
+/* host-side plan of yolo2_conv2d_wgrad_ws for a shape on a device with `cus` compute units (the function the workspace query and the launch use):
+ * out4 = {kernel family (0 image layer, 1 conv1's kernel, 2 row-of-taps kernel, 3 per-tap kernel), slots (1: single range, no workspace),
+ *         floats per slot, workgroups of the producer launch}.  After a yolo2_conv2d_wgrad_ws call yolo2_debug_last_wgrad_plan reports the plan words of
+ * yolo2_conv2d_wgrad with `pixel ranges` = slots; the image layer reports {8, 32, 4, 9, slots, 0, slots, 0} instead of all -1. */
+int yolo2_debug_wgrad_ws_plan(int B, int H, int W, int Cin, int ldx, int Cout, int ldy, int ksize, int dtype, int cus, int *out4);
 /* the multiply-high division constants of that kernel's DMA address arithmetic: floor(q / d) == (uint64(q) * m >> 32) >> s for 0 <= q < 2^31 */
 int yolo2_debug_magic_u32(unsigned d, unsigned *m, unsigned *s);
 

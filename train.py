@@ -54,6 +54,8 @@ def make_args():
     parser.add_argument('--data', default='cache', help="'cache' (default, as the reference's train.py:98-100: the TFRecord cache of the -p profiles under cachedir), "
                         "'synthetic' (random images and labels: benchmarking / smoke runs) or a .npz file")
     parser.add_argument('--dtype', default=None, choices=['bf16', 'f32'], help='overrides [mi355x] dtype')
+    parser.add_argument('--deterministic', action='store_true', help='bitwise reproducible training steps (also [mi355x] deterministic / YOLO2_DETERMINISTIC=1): '
+                        'filter gradients summed through a workspace in a fixed order, no float atomics anywhere in the step')
     parser.add_argument('--ckpt_format', default='npz', choices=['npz', 'tf'], help="checkpoint container: 'npz' (every optimizer) or 'tf' (TensorFlow V2 bundle, as the reference's tf.train.Saver writes)")
     return parser.parse_args()
 
@@ -133,7 +135,8 @@ def main():
                            bucket_mb=config.getfloat('mi355x', 'bucket_mb') if config.has_option('mi355x', 'bucket_mb') else 64.0,
                            grad_dtype=config.get('mi355x', 'grad_dtype') if config.has_option('mi355x', 'grad_dtype') else 'f32',
                            sync_bn=config.getboolean('mi355x', 'sync_bn') if config.has_option('mi355x', 'sync_bn') else False,
-                           shard_optimizer=config.getboolean('mi355x', 'shard_optimizer') if config.has_option('mi355x', 'shard_optimizer') else False)
+                           shard_optimizer=config.getboolean('mi355x', 'shard_optimizer') if config.has_option('mi355x', 'shard_optimizer') else False,
+                           deterministic=True if args.deterministic else None)      # (None: [mi355x] deterministic / YOLO2_DETERMINISTIC decide)
     logging.warning('optimizer=%s, dtype=%s, world=%d, parameters=%d' % (args.optimizer, dtype, world, session.engine.n_params))
     # rank 0 alone chooses and reads the checkpoint; the others receive parameters, statistics, optimizer slots and
     # global_step from it (same seed -> same initial weights anyway, but a restore must not depend on what each rank sees)

@@ -32,6 +32,8 @@ SIGNATURES = {
     'yolo2_bn_part_to_grads': [_p, _i, _p, _p, _p],
     'yolo2_debug_noop': [_p],
     'yolo2_conv2d_wgrad': [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    'yolo2_conv2d_wgrad_ws': [_p, _p, _p, _p, ctypes.c_size_t, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    'yolo2_set_deterministic': [_i],
     'yolo2_filter_prep': [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
     'yolo2_filter_prep_batch': [_p, _i, _i, _i, _p],
     'yolo2_adam_filter_prep': [_p, _i, _i, _p, _i, _p, _p, _p, _p, _f, _f, _f, _f, _f, _i, _p],
@@ -87,6 +89,7 @@ SIGNATURES = {
     'yolo2_adagrad': [_p, _p, _p, _l, _f, _f, _p],
     'yolo2_adadelta': [_p, _p, _p, _p, _l, _f, _f, _f, _f, _p],
     'yolo2_clip_by_norm': [_p, _p, _i, _f, _p, _p],
+    'yolo2_clip_by_norm_fixed': [_p, _p, _i, _f, _p, ctypes.c_size_t, _p],
     'yolo2_ftrl': [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _p],
     'yolo2_scale': [_p, _l, _f, _p],
     'yolo2_zero_ranges': [_p, _p, _i, _p],
@@ -121,6 +124,9 @@ QUERIES = {
     'yolo2_debug_set_s4_abl': (_i, [_i]),
     'yolo2_debug_last_wgrad_plan': (_i, [ctypes.POINTER(_i)]),
     'yolo2_debug_wgrad_row_plan': (_i, [_i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(_i)]),
+    'yolo2_debug_wgrad_ws_plan': (_i, [_i] * 10 + [ctypes.POINTER(_i)]),
+    'yolo2_conv2d_wgrad_workspace_bytes': (ctypes.c_size_t, [_i] * 9),
+    'yolo2_get_deterministic': (_i, []),
     'yolo2_debug_magic_u32': (_i, [ctypes.c_uint, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint)]),
     'yolo2_conv2d_workspace_bytes': (ctypes.c_size_t, [_i] * 7),
     'yolo2_bn_workspace_bytes': (ctypes.c_size_t, [_i]),
@@ -129,6 +135,7 @@ QUERIES = {
     'yolo2_loss_workspace_bytes': (ctypes.c_size_t, [_i, _i, _i]),
     'yolo2_nms_workspace_bytes': (ctypes.c_size_t, [_i, _i, _i]),
     'yolo2_clip_workspace_bytes': (ctypes.c_size_t, [_i]),
+    'yolo2_clip_fixed_workspace_bytes': (ctypes.c_size_t, [_i]),
     'yolo2_augment_workspace_bytes': (ctypes.c_size_t, [_i]),
 }
 

@@ -17,6 +17,7 @@ typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 void yolo2_set_error(const char *fmt, ...);
+int y2_deterministic();      // the calling thread's deterministic mode (yolo2_set_deterministic)
 
 #if defined(__HIP_DEVICE_COMPILE__)
 // ds_read_b64_tr_b16 through inline asm.  The builtin form is a compiler-visible LDS read: while an LDS-DMA (buffer_load ... lds)
@@ -110,7 +111,8 @@ template <int G> __device__ inline double y2_lane_group_sum_f64(double v) { retu
 bool y2_first_layer_shape(int Cp, int ldp, int Nf, int ldo, int ksize);
 int y2_first_layer_fwd(const void *P, const void *F, void *O, int B, int H, int W, int dtype, hipStream_t st,
                        const float *bn_shift = nullptr, float *bn_part = nullptr);
-int y2_first_layer_wgrad(const void *X, const void *dY, float *dW, int B, int H, int W, int Cin, int dtype, hipStream_t st);
+int y2_first_layer_wgrad(const void *X, const void *dY, float *dW, int B, int H, int W, int Cin, int dtype, hipStream_t st, float *ws = nullptr);      // ws: one slot per workgroup
+int y2_first_layer_wgrad_blocks(int B, int H, int W);
 
 // batch-norm partial sums produced by the convolution epilogue: [2][Y2_BN_PART_ROWS][C] f32 (elementwise.hip finalises)
 #define Y2_BN_PART_ROWS YOLO2_BN_PART_ROWS

@@ -339,7 +339,8 @@ __global__ __launch_bounds__(256) void conv_first_pool_kernel(const T *__restric
 // ---------------------------------------------------------------------------------------------------
 // filter gradient
 // ---------------------------------------------------------------------------------------------------
-template <typename T>
+// WS (workspace form): dW is the caller's workspace, workgroup b stores its 9 x Cin x 32 sums into slot b -- no atomic (wgrad_reduce_kernel sums the slots)
+template <typename T, bool WS = false>
 __global__ __launch_bounds__(256) void conv_first_wgrad_kernel(const T *__restrict__ X, unsigned x_bytes, const T *__restrict__ dY, unsigned y_bytes,
                                                                float *__restrict__ dW, int B, int H, int W, int Cin, int units) {
     constexpr int PXB = First<T>::PXB, HALO = First<T>::HALO;
@@ -465,7 +466,8 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_kernel(const T *__restri
 #ifdef Y2FIRST_ABL_NOATOMIC
                     if (v == 123.456f) dW[0] = v;
 #else
-                    unsafeAtomicAdd(dW + ((long)tap * Cin + c) * 32 + n, v);
+                    if constexpr (WS) dW[(long)blockIdx.x * (9 * Cin * 32) + ((long)tap * Cin + c) * 32 + n] = v;
+                    else unsafeAtomicAdd(dW + ((long)tap * Cin + c) * 32 + n, v);
 #endif
                 }
             }
@@ -725,9 +727,22 @@ int y2_first_layer_fwd(const void *P, const void *F, void *O, int B, int H, int 
     return 0;
 }
 
-int y2_first_layer_wgrad(const void *X, const void *dY, float *dW, int B, int H, int W, int Cin, int dtype, hipStream_t st) {
+// workgroups of the image layer's filter gradient (= slots of its workspace form)
+int y2_first_layer_wgrad_blocks(int B, int H, int W) {
     const int units = B * H * ((W + 31) / 32);
-    const int grid = units / 4 + 8 < 512 ? (units / 4 + 8) / 8 * 8 : 512;
+    return units / 4 + 8 < 512 ? (units / 4 + 8) / 8 * 8 : 512;
+}
+
+int y2_first_layer_wgrad(const void *X, const void *dY, float *dW, int B, int H, int W, int Cin, int dtype, hipStream_t st, float *ws) {
+    const int units = B * H * ((W + 31) / 32);
+    const int grid = y2_first_layer_wgrad_blocks(B, H, W);
+    if (ws) {      // workspace form: one slot per workgroup, the four waves of a workgroup meet in LDS first
+        if (dtype == YOLO2_BF16)
+            conv_first_wgrad_kernel<bf16, true><<<grid, 256, 0, st>>>((const bf16 *)X, (unsigned)((size_t)B * H * W * 8 * 2), (const bf16 *)dY, (unsigned)((size_t)B * H * W * 32 * 2), ws, B, H, W, Cin, units);
+        else
+            conv_first_wgrad_kernel<float, true><<<grid, 256, 0, st>>>((const float *)X, (unsigned)((size_t)B * H * W * 8 * 4), (const float *)dY, (unsigned)((size_t)B * H * W * 32 * 4), ws, B, H, W, Cin, units);
+        return 0;
+    }
     if (dtype == YOLO2_BF16)
         conv_first_wgrad_kernel<bf16><<<grid, 256, 0, st>>>((const bf16 *)X, (unsigned)((size_t)B * H * W * 8 * 2), (const bf16 *)dY, (unsigned)((size_t)B * H * W * 32 * 2), dW, B, H, W, Cin, units);
     else

@@ -351,6 +351,8 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(
             const long tile_end = su - kt_end + nk;       // su was already advanced past this segment
             const int G = gridDim.x;
             long covered = su;
+            // (deterministic mode relies on this: the parked parts are added in partner-index order p = wx + 1, wx + 2, ... whatever order
+            // their flags went up in, and the partition is a function of the shape and the grid alone -- the tile's sum has one fixed order)
             for (int p = wx + 1; covered < tile_end; ++p) {
                 if (tid == 0) y2_sk_wait_and_clear(flags, p);      // (bounded: conv_shared.h)
                 __syncthreads();
@@ -980,7 +982,8 @@ static int launch_conv(const void *P, const void *F, const float *bias, void *O,
         const int NT = cdiv(Nf, 128);
         // K slicing (grids <= 128 tiles with a long reduction) multiplies the workgroup count, so it pairs with the
         // narrow variant (3 workgroups per CU); unsliced small grids take the wide one.
-        int ks = ws ? choose_ksplit(MT * NT, ksize * ksize * cdiv(Cp, 4 * VEC), tu.target_blocks) : 1;
+        // (deterministic mode: no K slicing -- its slices meet in f32 atomics; stream-K or the unsplit grid instead)
+        int ks = (ws && !y2_deterministic()) ? choose_ksplit(MT * NT, ksize * ksize * cdiv(Cp, 4 * VEC), tu.target_blocks) : 1;
         if (ks > 1 && (size_t)M * Nf * sizeof(float) > ws_bytes) ks = 1;
         const bool wide = tu.wide && ks == 1 && MT * NT <= 256 && Cp % (8 * VEC) == 0;
         // stream-K: a grid that cannot give every CU a tile (13x13 stages at batch 16: 176 tiles, 88 for the narrower

@@ -510,6 +510,8 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(
                 __syncthreads();
                 Y2P_STAMP(3);
             }
+            // (deterministic mode relies on this: the parked parts are added in partner-index order p = wx + 1, wx + 2, ... whatever order
+            // their flags went up in, and the partition is a function of the shape and the grid alone -- the tile's sum has one fixed order)
             for (int p = wx + 1; covered < tile_end; ++p) {
                 const unsigned theirs = (unsigned)((size_t)p * SLOT * sizeof(float)) + slot_lane;
 #pragma unroll

@@ -385,6 +385,7 @@ __global__ __launch_bounds__(512) void conv3x3_s4_kernel(
             __syncthreads();
             Y2S_STAMP(3);
             if (comp_e) {
+                // (deterministic mode relies on this: the parked parts are added in partner-index order, whatever order their flags went up in)
                 for (int p = wx + 1; p <= wx + np_; ++p) {
                     const unsigned theirs = (unsigned)((size_t)p * SLOT * sizeof(float)) + slot_lane;
 #pragma unroll

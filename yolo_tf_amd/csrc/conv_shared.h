@@ -63,14 +63,19 @@ int y2_conv3x3_s4_launch(const void *P, unsigned p_bytes, const void *F, unsigne
 // taken (conv_wgrad.hip's per-tap kernel runs instead).
 struct Y2W3Plan { int variant, ks, qchunk, blocks, remap, direct, BC, BN, waves; };
 Y2W3Plan y2_wgrad3_plan(int B, int H, int W, int Cin, int Cout, int cus, int force_variant);
-int y2_wgrad3_launch(const Y2W3Plan &p, const void *X, const void *dY, float *dW, int B, int H, int W, int Cin, int ldx, int Cout, int ldy, hipStream_t st);
+// ws != nullptr (workspace form, a split plan only): the workgroup of pixel range r stores its partial tile into slot r of ws, nothing touches dW
+int y2_wgrad3_launch(const Y2W3Plan &p, const void *X, const void *dY, float *dW, int B, int H, int W, int Cin, int ldx, int Cout, int ldy, hipStream_t st,
+                     float *ws = nullptr);
+// Workspace form of the split filter gradients (yolo2_conv2d_wgrad_ws): floats between two slots of the workspace -- one filter gradient
+// [taps][Cin][Cout], rounded up to 16 bytes so that every slot can be read with 16-byte loads
+__host__ __device__ inline long y2_wgrad_slot_stride(int taps, int Cin, int Cout) { return ((long)taps * Cin * Cout + 3) & ~3L; }
 void y2_magic_u32(unsigned d, unsigned *m, unsigned *s);
 
 // conv_wgrad_c32.hip: 3x3 filter gradient for 32 input channels and 64 filters (Darknet-19 conv1), bf16: all nine taps in one workgroup over a run of image
 // rows, every operand byte read once.  y2_w32_wgrad returns non-zero when the rows do not fit its LDS plan (the caller then takes the per-tap kernel).
 bool y2_w32_shape(int Cin, int ldx, int Cout, int ldy, int ksize, int dtype);
 int y2_w32_blocks(int B, int H, int W, int cus);      // workgroups of the launch; 0: not taken
-int y2_w32_wgrad(const void *X, const void *dY, float *dW, int B, int H, int W, int cus, int *blocks, hipStream_t st);
+int y2_w32_wgrad(const void *X, const void *dY, float *dW, int B, int H, int W, int cus, int *blocks, hipStream_t st, float *ws = nullptr);      // ws: one slot per workgroup
 
 // conv_c32.hip: persistent 3x3 forward for 32-channel inputs and 64 filters (Darknet-19 conv1), bf16.  y2_c32_fwd returns non-zero when the image is
 // too wide for its LDS plan (the caller then takes the generic kernels).

@@ -38,7 +38,9 @@
 
 // PAIR (BC = 64, Cin <= 32): the 64 tile rows hold TWO taps x 32 channels (rows 0-31: tap 2p, rows 32-63: tap 2p+1), so a
 // 32-channel layer (conv1: 25 GFLOP) does not spend half of every MFMA on zero rows.
-template <typename T, int BC, int BNN, int VARIANT, int NW = 4, int BKPv = 0, bool PAIR = false>
+// WS (workspace form, yolo2_conv2d_wgrad_ws): ``dW`` is the caller's workspace and the block of pixel range ``by`` owns slot ``by`` of it
+// (slot layout = the layout of dW, slot stride y2_wgrad_slot_stride floats): plain stores, no atomic; wgrad_reduce_kernel sums the slots in range order.
+template <typename T, int BC, int BNN, int VARIANT, int NW = 4, int BKPv = 0, bool PAIR = false, bool WS = false>
 __global__ __launch_bounds__(NW * 64) void conv_wgrad_kernel(
     const T *__restrict__ X, unsigned x_bytes, const T *__restrict__ dY, unsigned y_bytes, float *__restrict__ dW, int H, int W,
     int Cin, int ldx, int Cout, int ldy, int ksize, int M, int CT, int NT, int mchunk, int remap, int direct) {
@@ -341,6 +343,7 @@ __global__ __launch_bounds__(NW * 64) void conv_wgrad_kernel(
     const int my_tap = PAIR ? tap + wm : tap;
     if (PAIR && my_tap >= taps) return;
     float *out = dW + (long)my_tap * Cin * Cout;
+    if constexpr (WS) out += (long)by * y2_wgrad_slot_stride(taps, Cin, Cout);
     auto write_tile = [&](auto checked_tag) {      // interior tiles skip the per-element channel tests (a branch each)
         constexpr bool CHECKED = decltype(checked_tag)::value;
 #pragma unroll
@@ -355,7 +358,7 @@ __global__ __launch_bounds__(NW * 64) void conv_wgrad_kernel(
                 for (int r = 0; r < 16; ++r) {
                     const int dc = (r & 3) + 8 * (r >> 2);
                     if (!CHECKED || cb + dc < Cin) {
-                        if (direct) col[(long)dc * Cout] = acc[i][j][r];      // single pixel range: this block owns the element
+                        if (WS || direct) col[(long)dc * Cout] = acc[i][j][r];      // single pixel range / own workspace slot: this block owns the element
                         else unsafeAtomicAdd(col + (long)dc * Cout, acc[i][j][r]);
                     }
                 }
@@ -382,14 +385,6 @@ static int wgrad_cus() {
         cached_cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
     }
     return cached_cus;
-}
-// the row-of-taps kernel (conv_wgrad3.hip) takes the bf16 3x3 layers beyond the image layer
-static Y2W3Plan wgrad_row_plan(int B, int H, int W, int Cin, int Cout, int ksize, int dtype) {
-    Y2W3Plan none = {};
-    none.variant = -1;
-    const int raw = g_wgrad_variant_raw.load(std::memory_order_relaxed);
-    if (dtype != YOLO2_BF16 || ksize != 3 || raw == 1 || raw == 2) return none;
-    return y2_wgrad3_plan(B, H, W, Cin, Cout, wgrad_cus(), raw >= 10 ? raw - 10 : -1);
 }
 // plan of the calling thread's most recent launch: {BC, BNN, waves, PAIR, pixel ranges, XCD remap, blocks, direct store}
 static thread_local int g_last_wgrad_plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -464,9 +459,10 @@ static WgradPlan wgrad_plan(int M, int Cin, int Cout, int ksize, int BC, int BNN
     return p;
 }
 
+// ws != nullptr: workspace form of a split plan (pixel range r stores into slot r of ws; the caller sums the slots into dW)
 template <typename T, int BC, int BNN, int BKPv = 0>
-static void launch_wgrad(const void *X, const void *dY, float *dW, int B, int H, int W, int Cin, int ldx,
-                         int Cout, int ldy, int ksize, hipStream_t st) {
+static int launch_wgrad(const void *X, const void *dY, float *dW, int B, int H, int W, int Cin, int ldx,
+                         int Cout, int ldy, int ksize, hipStream_t st, float *ws = nullptr) {
     const int M = B * H * W;
     const int CT = cdiv(Cin, BC), NT = cdiv(Cout, BNN);
     constexpr int BKP = BKPv ? BKPv : (sizeof(T) == 2 ? 32 : 16);
@@ -481,22 +477,48 @@ static void launch_wgrad(const void *X, const void *dY, float *dW, int B, int H,
         const int plan[8] = {BC, BNN, w8 ? 8 : 4, pair ? 1 : 0, pl.ks, remap, pl.blocks, direct};
         for (int i = 0; i < 8; ++i) g_last_wgrad_plan[i] = plan[i];
     }
+    if (ws && !direct) {
+        // the same tiles, ranges and block placement as the atomic form; only the epilogue differs
+        if constexpr (BKPv != 0) {
+            yolo2_set_error("filter gradient: the 64-pixel reduction tile has no workspace form (it is a single-range kernel)");
+            return YOLO2_E_UNSUPPORTED;
+        } else {
+#define Y2_WGRAD_WS_ARGS (const T *)X, x_bytes, (const T *)dY, y_bytes, ws, H, W, Cin, ldx, Cout, ldy, ksize, M, CT, NT, mchunk, remap, 0
+            if constexpr (BC >= 128) {
+                if (g_wgrad_variant == 0 && nw8) {
+                    conv_wgrad_kernel<T, BC, BNN, 0, 8, 0, false, true><<<grid, 512, 0, st>>>(Y2_WGRAD_WS_ARGS);
+                    return YOLO2_OK;
+                }
+            }
+            if constexpr (BC == 64) {
+                if (g_wgrad_variant == 0 && wgrad_pairs_taps(Cin, ksize)) {
+                    conv_wgrad_kernel<T, BC, BNN, 0, 4, 0, true, true><<<grid, 256, 0, st>>>(Y2_WGRAD_WS_ARGS);
+                    return YOLO2_OK;
+                }
+            }
+            if (g_wgrad_variant == 0) conv_wgrad_kernel<T, BC, BNN, 0, 4, 0, false, true><<<grid, 256, 0, st>>>(Y2_WGRAD_WS_ARGS);
+            else conv_wgrad_kernel<T, BC, BNN, 1, 4, 0, false, true><<<grid, 256, 0, st>>>(Y2_WGRAD_WS_ARGS);
+#undef Y2_WGRAD_WS_ARGS
+            return YOLO2_OK;
+        }
+    }
     if constexpr (BC >= 128) {
         if (g_wgrad_variant == 0 && nw8) {
             conv_wgrad_kernel<T, BC, BNN, 0, 8, BKPv><<<grid, 512, 0, st>>>((const T *)X, x_bytes, (const T *)dY, y_bytes, dW, H, W, Cin, ldx, Cout, ldy, ksize, M, CT, NT, mchunk, remap, direct);
-            return;
+            return YOLO2_OK;
         }
     }
     if constexpr (BC == 64) {
         if (g_wgrad_variant == 0 && wgrad_pairs_taps(Cin, ksize)) {
             conv_wgrad_kernel<T, BC, BNN, 0, 4, 0, true><<<grid, 256, 0, st>>>((const T *)X, x_bytes, (const T *)dY, y_bytes, dW, H, W, Cin, ldx, Cout, ldy, ksize, M, CT, NT, mchunk, remap, direct);
-            return;
+            return YOLO2_OK;
         }
     }
     if (g_wgrad_variant == 0)
         conv_wgrad_kernel<T, BC, BNN, 0, 4, BKPv><<<grid, 256, 0, st>>>((const T *)X, x_bytes, (const T *)dY, y_bytes, dW, H, W, Cin, ldx, Cout, ldy, ksize, M, CT, NT, mchunk, remap, direct);
     else
         conv_wgrad_kernel<T, BC, BNN, 1><<<grid, 256, 0, st>>>((const T *)X, x_bytes, (const T *)dY, y_bytes, dW, H, W, Cin, ldx, Cout, ldy, ksize, M, CT, NT, mchunk, remap, direct);
+    return YOLO2_OK;
 }
 
 static bool wgrad_small_tile(int Cin, int Cout, int ksize) {
@@ -506,22 +528,84 @@ static bool wgrad_small_tile(int Cin, int Cout, int ksize) {
     return Cin <= 64 || Cout <= 64 || ksize * ksize * cdiv(Cin, 128) * cdiv(Cout, 128) < small_below;
 }
 
+static int wgrad_per_tap(const void *X, const void *dY, float *dW, int B, int H, int W, int Cin, int ldx, int Cout, int ldy, int ksize, int dtype, hipStream_t st,
+                         float *ws);
+
+// Which kernel family takes a shape and how many partial results ("slots") its launch leaves: pixel ranges of the per-tap and the row kernel, workgroups of
+// conv1's kernel and of the image layer's.  The ONE selection in this file: yolo2_conv2d_wgrad, yolo2_conv2d_wgrad_accumulates, the workspace query, the
+// workspace launch and the host plan query (yolo2_debug_wgrad_ws_plan) all read it.  family: 0 = image layer (conv_first.hip), 1 = conv1 (conv_wgrad_c32.hip), 2 = row kernel
+// (conv_wgrad3.hip), 3 = per-tap kernel (this file).  slots == 1: the launch stores into dW itself, no workspace.
+struct WgradRoute { int family, slots; long slot_floats; Y2W3Plan rp; int plan[8]; };
+static WgradRoute wgrad_route(int B, int H, int W, int Cin, int ldx, int Cout, int ldy, int ksize, int dtype, int cus) {
+    WgradRoute r = {};
+    r.slot_floats = y2_wgrad_slot_stride(ksize * ksize, Cin, Cout);
+    static const bool first_direct = y2_env_int("YOLO2_FIRST_DIRECT", 1) != 0;
+    const int raw = g_wgrad_variant_raw.load(std::memory_order_relaxed);
+    if (first_direct && Cin <= 8 && y2_first_layer_shape(8, ldx, Cout, ldy, ksize)) {
+        r.family = 0;
+        r.slots = y2_first_layer_wgrad_blocks(B, H, W);
+        const int plan[8] = {8, 32, 4, 9, r.slots, 0, r.slots, r.slots == 1};
+        for (int i = 0; i < 8; ++i) r.plan[i] = plan[i];
+        return r;
+    }
+    if (raw == 0 && y2_w32_shape(Cin, ldx, Cout, ldy, ksize, dtype)) {
+        const int blocks = y2_w32_blocks(B, H, W, cus);
+        if (blocks > 0) {
+            r.family = 1;
+            r.slots = blocks;
+            const int plan[8] = {32, 64, 12, 9, blocks, 0, blocks, blocks == 1};
+            for (int i = 0; i < 8; ++i) r.plan[i] = plan[i];
+            return r;
+        }
+    }
+    if (dtype == YOLO2_BF16 && ksize == 3 && raw != 1 && raw != 2) {      // the row-of-taps kernel (conv_wgrad3.hip) takes the bf16 3x3 layers beyond the image layer
+        r.rp = y2_wgrad3_plan(B, H, W, Cin, Cout, cus, raw >= 10 ? raw - 10 : -1);
+        if (r.rp.variant >= 0) {
+            r.family = 2;
+            r.slots = r.rp.ks;
+            const int plan[8] = {r.rp.BC, r.rp.BN, r.rp.waves, 3, r.rp.ks, r.rp.remap, r.rp.blocks, r.rp.direct};      // "pair" slot 3: three taps (a kernel row) per workgroup
+            for (int i = 0; i < 8; ++i) r.plan[i] = plan[i];
+            return r;
+        }
+    }
+    r.family = 3;
+    const bool small = wgrad_small_tile(Cin, Cout, ksize);
+    const WgradPlan pl = wgrad_plan(B * H * W, Cin, Cout, ksize, small ? 64 : 128, small ? 64 : 128, dtype == YOLO2_BF16 ? 32 : 16);
+    r.slots = pl.ks;
+    const int plan[8] = {small ? 64 : 128, small ? 64 : 128, 0, 0, pl.ks, pl.remap, pl.blocks, pl.ks == 1};      // (waves / pair: filled in by the launch)
+    for (int i = 0; i < 8; ++i) r.plan[i] = plan[i];
+    return r;
+}
+// Launches what the route names.  ws == nullptr: the form yolo2_conv2d_wgrad has always launched (atomic epilogue for a split plan, plain stores for a
+// single range); ws != nullptr (a split plan only): every partial result into its own slot of ws, nothing touches dW.
+static int wgrad_launch(const WgradRoute &r, const void *X, const void *dY, float *dW, int B, int H, int W, int Cin, int ldx, int Cout, int ldy, int ksize,
+                        int dtype, hipStream_t st, float *ws) {
+    for (int i = 0; i < 8; ++i) g_last_wgrad_plan[i] = (r.family == 0 && !ws) ? -1 : r.plan[i];
+    switch (r.family) {
+        case 0: y2_first_layer_wgrad(X, dY, dW, B, H, W, Cin, dtype, st, ws); break;      // image layer: direct kernel (conv_first.hip)
+        case 1: {                                                                       // conv1: all nine taps per workgroup (conv_wgrad_c32.hip)
+            int blocks = 0;
+            if (y2_w32_wgrad(X, dY, dW, B, H, W, wgrad_cus(), &blocks, st, ws) == 0) {
+                if (ws && blocks != r.slots) { yolo2_set_error("filter gradient: conv1 kernel launched %d workgroups for %d slots", blocks, r.slots); return YOLO2_E_LAUNCH; }
+                break;
+            }
+            if (ws) { yolo2_set_error("filter gradient: conv1 kernel not launched"); return YOLO2_E_LAUNCH; }
+            return wgrad_per_tap(X, dY, dW, B, H, W, Cin, ldx, Cout, ldy, ksize, dtype, st, nullptr);      // (its LDS could not be set up: the per-tap kernel, as before)
+        }
+        case 2:
+            if (y2_wgrad3_launch(r.rp, X, dY, dW, B, H, W, Cin, ldx, Cout, ldy, st, ws) != 0) { yolo2_set_error("yolo2_conv2d_wgrad: no such row-kernel variant"); return YOLO2_E_ARG; }
+            break;
+        default: return wgrad_per_tap(X, dY, dW, B, H, W, Cin, ldx, Cout, ldy, ksize, dtype, st, ws);      // (writes the plan of its launch)
+    }
+    Y2_CHECK_LAUNCH();
+    return YOLO2_OK;
+}
+
 extern "C" int yolo2_conv2d_wgrad_accumulates(int B, int H, int W, int Cin, int ldx, int Cout, int ldy, int ksize, int dtype) {
     if (!(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0) || !(ksize == 1 || ksize == 3) || !(dtype == YOLO2_F32 || dtype == YOLO2_BF16)) return 1;
-    static const bool first_direct = y2_env_int("YOLO2_FIRST_DIRECT", 1) != 0;
-    if (first_direct && Cin <= 8 && y2_first_layer_shape(8, ldx, Cout, ldy, ksize)) return 1;      // cross-workgroup atomics
-    if (g_wgrad_variant != 0) return 1;
-    if (g_wgrad_variant_raw.load(std::memory_order_relaxed) == 0 && y2_w32_shape(Cin, ldx, Cout, ldy, ksize, dtype)) {
-        const int blocks = y2_w32_blocks(B, H, W, wgrad_cus());
-        if (blocks > 0) return blocks == 1 ? 0 : 1;                  // one workgroup stores, several add
-    }
-    {
-        const Y2W3Plan rp = wgrad_row_plan(B, H, W, Cin, Cout, ksize, dtype);
-        if (rp.variant >= 0) return rp.direct ? 0 : 1;
-    }
-    const int bkp = dtype == YOLO2_BF16 ? 32 : 16;
-    const bool small = wgrad_small_tile(Cin, Cout, ksize);
-    return wgrad_plan(B * H * W, Cin, Cout, ksize, small ? 64 : 128, small ? 64 : 128, bkp).ks == 1 ? 0 : 1;
+    const WgradRoute r = wgrad_route(B, H, W, Cin, ldx, Cout, ldy, ksize, dtype, wgrad_cus());
+    if (r.family != 0 && g_wgrad_variant != 0) return 1;      // (scalar-gather test hook: be safe, clear)
+    return r.slots > 1 ? 1 : 0;                               // several pixel ranges / workgroups add into dW; one stores
 }
 
 extern "C" int yolo2_conv2d_wgrad(const void *X, const void *dY, float *dW, int B, int H, int W, int Cin,
@@ -530,42 +614,23 @@ extern "C" int yolo2_conv2d_wgrad(const void *X, const void *dY, float *dW, int 
     Y2_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0);
     Y2_CHECK_ARG(ksize == 1 || ksize == 3);
     Y2_CHECK_ARG(ldx >= Cin && ldy >= Cout);
+    Y2_CHECK_ARG(dtype == YOLO2_F32 || dtype == YOLO2_BF16);
     const int vec = dtype == YOLO2_BF16 ? 8 : 4;
     const size_t esz = dtype == YOLO2_BF16 ? 2 : 4;
     Y2_CHECK_ARG(ldx % vec == 0 && ldy % vec == 0);
     Y2_CHECK_ARG(((uintptr_t)X & 15) == 0 && ((uintptr_t)dY & 15) == 0);
     // 32-bit byte offsets below 2^31 on both operands (DMA descriptors)
     Y2_CHECK_ARG((size_t)B * H * W * (size_t)(ldx > ldy ? ldx : ldy) * esz < (1ull << 31));
-    hipStream_t st = (hipStream_t)stream;
-    static const bool first_direct = y2_env_int("YOLO2_FIRST_DIRECT", 1) != 0;
-    if (first_direct && Cin <= 8 && y2_first_layer_shape(8, ldx, Cout, ldy, ksize) && (dtype == YOLO2_F32 || dtype == YOLO2_BF16)) {
-        y2_first_layer_wgrad(X, dY, dW, B, H, W, Cin, dtype, st);                       // image layer: direct kernel (conv_first.hip)
-        for (int i = 0; i < 8; ++i) g_last_wgrad_plan[i] = -1;
-        Y2_CHECK_LAUNCH();
-        return YOLO2_OK;
-    }
-    if (g_wgrad_variant_raw.load(std::memory_order_relaxed) == 0 && y2_w32_shape(Cin, ldx, Cout, ldy, ksize, dtype)) {
-        int blocks = 0;                                                                 // conv1: all nine taps per workgroup (conv_wgrad_c32.hip)
-        if (y2_w32_wgrad(X, dY, dW, B, H, W, wgrad_cus(), &blocks, st) == 0) {
-            const int plan[8] = {32, 64, 12, 9, blocks, 0, blocks, blocks == 1};
-            for (int i = 0; i < 8; ++i) g_last_wgrad_plan[i] = plan[i];
-            Y2_CHECK_LAUNCH();
-            return YOLO2_OK;
-        }
-    }
-    {
-        const Y2W3Plan rp = wgrad_row_plan(B, H, W, Cin, Cout, ksize, dtype);
-        if (rp.variant >= 0) {
-            const int plan[8] = {rp.BC, rp.BN, rp.waves, 3, rp.ks, rp.remap, rp.blocks, rp.direct};      // "pair" slot 3: three taps (a kernel row) per workgroup
-            for (int i = 0; i < 8; ++i) g_last_wgrad_plan[i] = plan[i];
-            if (y2_wgrad3_launch(rp, X, dY, dW, B, H, W, Cin, ldx, Cout, ldy, st) != 0) { yolo2_set_error("yolo2_conv2d_wgrad: no such row-kernel variant"); return YOLO2_E_ARG; }
-            Y2_CHECK_LAUNCH();
-            return YOLO2_OK;
-        }
-    }
+    const WgradRoute r = wgrad_route(B, H, W, Cin, ldx, Cout, ldy, ksize, dtype, wgrad_cus());
+    return wgrad_launch(r, X, dY, dW, B, H, W, Cin, ldx, Cout, ldy, ksize, dtype, (hipStream_t)stream, nullptr);
+}
+
+static int wgrad_per_tap(const void *X, const void *dY, float *dW, int B, int H, int W, int Cin, int ldx, int Cout, int ldy, int ksize, int dtype, hipStream_t st,
+                         float *ws) {
     const bool small = wgrad_small_tile(Cin, Cout, ksize);
+    int rc = YOLO2_OK;
     if (small) {
-        Y2_DISPATCH_DTYPE(dtype, launch_wgrad<T, 64, 64>(X, dY, dW, B, H, W, Cin, ldx, Cout, ldy, ksize, st));
+        Y2_DISPATCH_DTYPE(dtype, rc = launch_wgrad<T, 64, 64>(X, dY, dW, B, H, W, Cin, ldx, Cout, ldy, ksize, st, ws));
     } else {
         // 64-pixel reduction tiles on a 2-stage ring (8 MFMAs per wave between barriers, same 64 KiB of LDS): pays when the launch gives
         // a CU about one workgroup -- single-range grids of up to 1.5 blocks per CU (the 512 -> 1024 13x13 layers: 41.9 -> 36.6 us);
@@ -576,9 +641,109 @@ extern "C" int yolo2_conv2d_wgrad(const void *X, const void *dY, float *dW, int 
             const WgradPlan pl = wgrad_plan(B * H * W, Cin, Cout, ksize, 128, 128, 32);
             use64 = pl.ks == 1 && 2 * pl.blocks <= 3 * cached_cus;
         }
-        if (use64 && dtype == YOLO2_BF16) launch_wgrad<bf16, 128, 128, 64>(X, dY, dW, B, H, W, Cin, ldx, Cout, ldy, ksize, st);
-        else Y2_DISPATCH_DTYPE(dtype, launch_wgrad<T, 128, 128>(X, dY, dW, B, H, W, Cin, ldx, Cout, ldy, ksize, st));
+        if (use64 && dtype == YOLO2_BF16) rc = launch_wgrad<bf16, 128, 128, 64>(X, dY, dW, B, H, W, Cin, ldx, Cout, ldy, ksize, st, ws);      // (single range by its rule; it refuses a split workspace launch)
+        else Y2_DISPATCH_DTYPE(dtype, rc = launch_wgrad<T, 128, 128>(X, dY, dW, B, H, W, Cin, ldx, Cout, ldy, ksize, st, ws));
     }
+    if (rc != YOLO2_OK) return rc;
+    Y2_CHECK_LAUNCH();
+    return YOLO2_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Workspace form: split filter gradients summed in a fixed order (deterministic training mode)
+// ---------------------------------------------------------------------------------------------------
+static bool wgrad_shape_ok(int B, int H, int W, int Cin, int ldx, int Cout, int ldy, int ksize, int dtype) {
+    if (!(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0) || !(ksize == 1 || ksize == 3) || !(dtype == YOLO2_F32 || dtype == YOLO2_BF16)) return false;
+    const int vec = dtype == YOLO2_BF16 ? 8 : 4;
+    if (ldx < Cin || ldy < Cout || ldx % vec != 0 || ldy % vec != 0) return false;
+    return (size_t)B * H * W * (size_t)(ldx > ldy ? ldx : ldy) * (dtype == YOLO2_BF16 ? 2 : 4) < (1ull << 31);
+}
+
+// dW[i] = slot[0][i] + slot[1][i] + ... + slot[ks-1][i]: thread (x, y) of a workgroup owns four consecutive elements and the contiguous run of slots
+// y * per .. (y + 1) * per - 1, which it adds in ascending order into one f32 chain; the RG chains of an element then meet in LDS and are added in ascending
+// y.  RG = 4 from 16 slots on (conv1's and the image layer's hundreds of slots: four times the loads in flight), RG = 1 -- 64-thread workgroups, one chain,
+// no LDS, no idle thread -- for the few ranges of the per-tap and row kernels.  The order is a function of ks alone -- not of arrival, placement or
+// addresses.  Every slot element is read once (16-byte loads), dW is written once and never read.
+template <bool VEC4, int RG>
+__global__ __launch_bounds__(64 * RG) void wgrad_reduce_kernel(const float *__restrict__ ws, float *__restrict__ dW, long n, long stride, int ks, int per) {
+    __shared__ f32x4 part[RG][64];
+    const int x = threadIdx.x & 63, y = threadIdx.x >> 6;
+    const long i = ((long)blockIdx.x * 64 + x) * 4;
+    f32x4 a = {0.f, 0.f, 0.f, 0.f};
+    const int s0 = y * per, s1 = min(ks, s0 + per);
+    if (i < n) {
+        const float *p = ws + (long)s0 * stride + i;
+        if (VEC4 || i + 4 <= n) {
+#pragma unroll 8
+            for (int s = s0; s < s1; ++s, p += stride) {
+                const f32x4 v = *reinterpret_cast<const f32x4 *>(p);      // (slots start 16-byte aligned: stride % 4 == 0, ws aligned)
+                a[0] += v[0]; a[1] += v[1]; a[2] += v[2]; a[3] += v[3];
+            }
+        } else {
+            for (int s = s0; s < s1; ++s, p += stride)
+                for (int k = 0; k < 4; ++k)
+                    if (i + k < n) a[k] += p[k];
+        }
+    }
+    if constexpr (RG > 1) {
+        part[y][x] = a;
+        __syncthreads();
+        if (y != 0) return;
+#pragma unroll
+        for (int g = 1; g < RG; ++g) {
+            const f32x4 v = part[g][x];
+            a[0] += v[0]; a[1] += v[1]; a[2] += v[2]; a[3] += v[3];
+        }
+    }
+    if (i >= n) return;
+    if (VEC4) *reinterpret_cast<f32x4 *>(dW + i) = a;
+    else
+        for (int k = 0; k < 4; ++k)
+            if (i + k < n) dW[i + k] = a[k];
+}
+static void launch_wgrad_reduce(const float *ws, float *dW, long n, long stride, int ks, hipStream_t st) {
+    const int grid = cdiv(n, 256);
+    const bool vec4 = n % 4 == 0 && ((uintptr_t)dW & 15) == 0;
+    if (ks >= 16) {
+        const int per = cdiv(ks, 4);
+        if (vec4) wgrad_reduce_kernel<true, 4><<<grid, 256, 0, st>>>(ws, dW, n, stride, ks, per);
+        else wgrad_reduce_kernel<false, 4><<<grid, 256, 0, st>>>(ws, dW, n, stride, ks, per);
+    } else {
+        if (vec4) wgrad_reduce_kernel<true, 1><<<grid, 64, 0, st>>>(ws, dW, n, stride, ks, ks);
+        else wgrad_reduce_kernel<false, 1><<<grid, 64, 0, st>>>(ws, dW, n, stride, ks, ks);
+    }
+}
+
+extern "C" size_t yolo2_conv2d_wgrad_workspace_bytes(int B, int H, int W, int Cin, int ldx, int Cout, int ldy, int ksize, int dtype) {
+    if (!wgrad_shape_ok(B, H, W, Cin, ldx, Cout, ldy, ksize, dtype)) return 0;
+    const WgradRoute r = wgrad_route(B, H, W, Cin, ldx, Cout, ldy, ksize, dtype, wgrad_cus());
+    return r.slots > 1 ? (size_t)r.slots * (size_t)r.slot_floats * sizeof(float) : 0;
+}
+
+// host-side plan of the workspace form for ``cus`` compute units, for tests without a GPU: out4 = {family, slots, floats per slot, launch blocks}
+extern "C" int yolo2_debug_wgrad_ws_plan(int B, int H, int W, int Cin, int ldx, int Cout, int ldy, int ksize, int dtype, int cus, int *out4) {
+    if (!out4 || cus < 1 || !wgrad_shape_ok(B, H, W, Cin, ldx, Cout, ldy, ksize, dtype)) return YOLO2_E_ARG;
+    const WgradRoute r = wgrad_route(B, H, W, Cin, ldx, Cout, ldy, ksize, dtype, cus);
+    out4[0] = r.family; out4[1] = r.slots; out4[2] = (int)r.slot_floats; out4[3] = r.plan[6];
+    return YOLO2_OK;
+}
+
+extern "C" int yolo2_conv2d_wgrad_ws(const void *X, const void *dY, float *dW, float *ws, size_t ws_bytes, int B, int H, int W, int Cin, int ldx, int Cout,
+                                     int ldy, int ksize, int dtype, void *stream) {
+    Y2_CHECK_ARG(X && dY && dW);
+    Y2_CHECK_ARG(wgrad_shape_ok(B, H, W, Cin, ldx, Cout, ldy, ksize, dtype));
+    Y2_CHECK_ARG(((uintptr_t)X & 15) == 0 && ((uintptr_t)dY & 15) == 0);
+    const WgradRoute r = wgrad_route(B, H, W, Cin, ldx, Cout, ldy, ksize, dtype, wgrad_cus());
+    hipStream_t st = (hipStream_t)stream;
+    if (r.slots <= 1) return wgrad_launch(r, X, dY, dW, B, H, W, Cin, ldx, Cout, ldy, ksize, dtype, st, nullptr);      // one writer per element already
+    const size_t need = (size_t)r.slots * (size_t)r.slot_floats * sizeof(float);
+    if (!ws || ws_bytes < need || ((uintptr_t)ws & 15) != 0) {
+        yolo2_set_error("yolo2_conv2d_wgrad_ws: workspace of %zu bytes needed (16-byte aligned), got %zu", need, ws ? ws_bytes : (size_t)0);
+        return YOLO2_E_ARG;
+    }
+    const int rc = wgrad_launch(r, X, dY, dW, B, H, W, Cin, ldx, Cout, ldy, ksize, dtype, st, ws);
+    if (rc != YOLO2_OK) return rc;
+    launch_wgrad_reduce(ws, dW, (long)ksize * ksize * Cin * Cout, r.slot_floats, r.slots, st);
     Y2_CHECK_LAUNCH();
     return YOLO2_OK;
 }

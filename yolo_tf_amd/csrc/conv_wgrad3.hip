@@ -53,7 +53,8 @@ __device__ __forceinline__ unsigned y2_div_magic(unsigned q, unsigned m, unsigne
 // 8 = DMA pieces issued with a constant source offset (no address arithmetic), 16 = no barrier, 32 = no output stores, 64 = no wave-group reduction,
 // 128 = no prologue DMA either, 256 = the workgroup returns at once (launch cost of the geometry), 512 = s_memtime stamps at the phase boundaries of
 // every super-step; each wave leaves {kernel, wait + barrier, DMA issue, reads + MFMA issue, table build, prologue, epilogue} cycle sums in dW (scripts/w3_phase_cycles.py)
-template <int WC, int WN, int KW, int P, int NSTAGE, int ABL = 0>
+// WS (workspace form): dW is the caller's workspace, the workgroup of pixel range ``by`` stores into slot ``by`` (stride y2_wgrad_slot_stride): no atomic.
+template <int WC, int WN, int KW, int P, int NSTAGE, int ABL = 0, bool WS = false>
 __global__ __launch_bounds__(WC *WN *KW * 64) void conv_wgrad_row_kernel(
     const bf16 *__restrict__ X, unsigned x_bytes, const bf16 *__restrict__ dY, unsigned y_bytes, float *__restrict__ dW, int H, int W, int Cin, int ldx,
     int Cout, int ldy, int Mp, int CT, int NT, int qchunk, int KS, int remap, int direct, unsigned mW, unsigned sW, unsigned mH, unsigned sH) {
@@ -476,6 +477,7 @@ __global__ __launch_bounds__(WC *WN *KW * 64) void conv_wgrad_row_kernel(
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
             float *out = dW + (long)((dh + 1) * 3 + d) * Cin * Cout;
+            if constexpr (WS) out += (long)by * y2_wgrad_slot_stride(9, Cin, Cout);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const int n = n0 + (wn * 2 + j) * 32 + (lane & 31);
@@ -486,7 +488,7 @@ __global__ __launch_bounds__(WC *WN *KW * 64) void conv_wgrad_row_kernel(
                 for (int r = 0; r < 16; ++r) {
                     const int dc = (r & 3) + 8 * (r >> 2);
                     if (!CHECKED || cb + dc < Cin) {
-                        if (direct) colp[(long)dc * Cout] = acc[d][j][r];      // single pixel range: this workgroup owns the element
+                        if (WS || direct) colp[(long)dc * Cout] = acc[d][j][r];      // single pixel range / own workspace slot: this workgroup owns the element
                         else unsafeAtomicAdd(colp + (long)dc * Cout, acc[d][j][r]);
                     }
                 }
@@ -577,7 +579,8 @@ Y2W3Plan y2_wgrad3_plan(int B, int H, int W, int Cin, int Cout, int cus, int for
     return p;
 }
 
-int y2_wgrad3_launch(const Y2W3Plan &p, const void *X, const void *dY, float *dW, int B, int H, int W, int Cin, int ldx, int Cout, int ldy, hipStream_t st) {
+int y2_wgrad3_launch(const Y2W3Plan &p, const void *X, const void *dY, float *dW, int B, int H, int W, int Cin, int ldx, int Cout, int ldy, hipStream_t st,
+                     float *ws) {
     const Y2W3Geom &gm = g_w3_geom[p.variant];
     const int Mp = B * H * (W + 1), CT = cdiv(Cin, gm.BC), NT = cdiv(Cout, gm.BN);
     const unsigned x_bytes = (unsigned)((size_t)B * H * W * ldx * 2), y_bytes = (unsigned)((size_t)B * H * W * ldy * 2);
@@ -615,6 +618,20 @@ int y2_wgrad3_launch(const Y2W3Plan &p, const void *X, const void *dY, float *dW
     if (abl && p.variant == 5) { Y2W3_ABL_CASES(2, 1, 4, 64, 2) }
     if (abl == 512 && p.variant == 4) { Y2W3_ABL(4, 2, 1, 64, 3, 512); return 0; }
 #endif
+#define Y2W3_LAUNCH_WS(WCv, WNv, KWv, Pv, NSv)                                                                                                      \
+    conv_wgrad_row_kernel<WCv, WNv, KWv, Pv, NSv, 0, true><<<dim3(p.blocks), WCv * WNv * KWv * 64, 0, st>>>((const bf16 *)X, x_bytes, (const bf16 *)dY, y_bytes, ws, H, W, \
+                                                                                                            Cin, ldx, Cout, ldy, Mp, CT, NT, p.qchunk, p.ks, p.remap, 0, mW, sW, mH, sH)
+    if (ws) {       // workspace form: the instantiations a split plan can name
+        if (p.direct) return 1;
+        switch (p.variant) {
+            case 2: Y2W3_LAUNCH_WS(2, 2, 2, 64, 3); break;
+            case 4: Y2W3_LAUNCH_WS(4, 2, 1, 64, 3); break;
+            case 5: Y2W3_LAUNCH_WS(2, 1, 4, 64, 2); break;
+            default: return 1;
+        }
+        return 0;
+    }
+#undef Y2W3_LAUNCH_WS
     switch (p.variant) {
 #ifdef Y2W3_EXPERIMENTS
         case 0: Y2W3_LAUNCH(1, 1, 8, 32, 2); break;

@@ -35,7 +35,8 @@ struct W32Geo {
 // D: image rows in flight ahead of the one being multiplied (2 where LDS allows: W <= 224).  ABL (timing ablations of -DY2W32_EXPERIMENTS builds, results
 // wrong by design): 1 = no MFMA, 2 = no fragment reads, 4 = no DMA inside the loop, 32 = no output, 64 = no pixel-group reduction, 256 = the workgroup returns at once,
 // 512 = wall-clock (100 MHz) stamps: every wave leaves {kernel, prologue, row loop, drain + first barrier, LDS reduction, atomics issued + acknowledged} cycles behind dW (the caller allocates 18432 + blocks x 12 x 16 floats)
-template <int D, int ABL = 0>
+// WS (workspace form): dW is the caller's workspace and workgroup b stores its 18432 sums into slot b of it -- no atomic (wgrad_reduce_kernel sums the slots).
+template <int D, int ABL = 0, bool WS = false>
 __global__ __launch_bounds__(768) void conv_wgrad_c32_kernel(const bf16 *__restrict__ X, unsigned x_bytes, const bf16 *__restrict__ dY, unsigned y_bytes,
                                                              float *__restrict__ dW, W32Geo g) {
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
@@ -255,7 +256,7 @@ __global__ __launch_bounds__(768) void conv_wgrad_c32_kernel(const bf16 *__restr
         constexpr bool DIRECT = decltype(direct_)::value;
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
-            float *out = dW + (kr * 3 + d) * (32 * 64) + (4 * (lane >> 5)) * 64 + (lane & 31);
+            float *out = dW + (WS ? (long)blockIdx.x * (9 * 32 * 64) : 0L) + (kr * 3 + d) * (32 * 64) + (4 * (lane >> 5)) * 64 + (lane & 31);
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -266,7 +267,7 @@ __global__ __launch_bounds__(768) void conv_wgrad_c32_kernel(const bf16 *__restr
                 }
         }
     };
-    if (gridDim.x == 1) write_out(std::true_type{});       // one workgroup: it owns dW (which may be dirty)
+    if (WS || gridDim.x == 1) write_out(std::true_type{});       // one workgroup: it owns dW (which may be dirty); workspace form: it owns its slot
     else write_out(std::false_type{});
     if constexpr (ABL & 512) {
         __builtin_amdgcn_sched_barrier(0);
@@ -315,7 +316,7 @@ int y2_w32_blocks(int B, int H, int W, int cus) {
 }
 
 // 0: launched (grid in *blocks).  Non-zero: not taken (see w32_plan)
-int y2_w32_wgrad(const void *X, const void *dY, float *dW, int B, int H, int W, int cus, int *blocks, hipStream_t st) {
+int y2_w32_wgrad(const void *X, const void *dY, float *dW, int B, int H, int W, int cus, int *blocks, hipStream_t st, float *ws) {
     W32Geo g;
     int D;
     size_t lds;
@@ -350,6 +351,22 @@ int y2_w32_wgrad(const void *X, const void *dY, float *dW, int B, int H, int W, 
 #undef W32_LAUNCH_ABL
     }
 #endif
+    if (ws && grid > 1) {      // workspace form: one slot per workgroup
+        static std::atomic<size_t> lds_set_ws[2][64];
+#define W32_LAUNCH_WS(Dv)                                                                                                                     \
+    do {                                                                                                                                      \
+        if (lds > lds_set_ws[Dv - 1][dev].load(std::memory_order_relaxed)) {                                                                  \
+            if (hipFuncSetAttribute((const void *)conv_wgrad_c32_kernel<Dv, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 1; \
+            lds_set_ws[Dv - 1][dev].store(lds, std::memory_order_relaxed);                                                                    \
+        }                                                                                                                                     \
+        conv_wgrad_c32_kernel<Dv, 0, true><<<grid, 768, lds, st>>>((const bf16 *)X, x_bytes, (const bf16 *)dY, y_bytes, ws, g);               \
+    } while (0)
+        if (D == 2) W32_LAUNCH_WS(2);
+        else W32_LAUNCH_WS(1);
+#undef W32_LAUNCH_WS
+        if (blocks) *blocks = grid;
+        return 0;
+    }
     if (D == 2) W32_LAUNCH(2);
     else W32_LAUNCH(1);
 #undef W32_LAUNCH

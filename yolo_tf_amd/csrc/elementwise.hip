@@ -27,6 +27,13 @@ void yolo2_set_error(const char *fmt, ...) {
 }
 extern "C" const char *yolo2_last_error(void) { return g_err; }
 
+// deterministic mode of the CALLING THREAD (include/yolo2_hip.h yolo2_set_deterministic): launch rules and reductions that would sum floats in arrival
+// order take a fixed-order form instead.  Thread-local like the error string; a deterministic engine switches it on for the duration of its own sweeps only.
+static thread_local int g_deterministic = 0;
+int y2_deterministic() { return g_deterministic; }
+extern "C" int yolo2_set_deterministic(int on) { g_deterministic = on ? 1 : 0; return YOLO2_OK; }
+extern "C" int yolo2_get_deterministic(void) { return g_deterministic; }
+
 // CRC32C (Castagnoli) of a HOST buffer, slicing-by-8: the checksum of TFRecord / TensorBoard event / TF checkpoint files
 // (utils/tfrecord.py, utils/events.py, tf_checkpoint.py); `crc` = value so far (0 to start).  ~1.5 GB/s, against ~1 MB/s in Python.
 extern "C" uint32_t yolo2_crc32c(const void *data, size_t n, uint32_t crc) {
@@ -1845,6 +1852,34 @@ __global__ void seg_sumsq_kernel(const float *__restrict__ g, const long *__rest
     acc = wave_sum_d(acc);
     if ((threadIdx.x & 63) == 0 && acc != 0.0) atomicAdd(ws + s, acc);
 }
+// fixed-order, two-level form (deterministic mode, yolo2_clip_by_norm_fixed): the same 64 workgroups per segment as above, but workgroup b STORES its sum
+// into part[s][b] -- thread chains over a fixed stride, wave_sum_d's fixed butterfly, the four wave sums added in wave order -- and the scale pass adds a
+// segment's 64 partials in index order (every thread the same 64 loads from L2).  One writer per partial, no atomic, no clearing.
+#define Y2_CLIP_PARTS 64
+__global__ __launch_bounds__(256) void seg_sumsq_part_kernel(const float *__restrict__ g, const long *__restrict__ seg_off, double *__restrict__ part) {
+    __shared__ double wsum[4];
+    const int s = blockIdx.y;
+    const long beg = seg_off[s], end = seg_off[s + 1];
+    double acc = 0.0;
+    for (long i = beg + blockIdx.x * 256L + threadIdx.x; i < end; i += (long)Y2_CLIP_PARTS * 256) {
+        const double v = (double)g[i];
+        acc += v * v;
+    }
+    acc = wave_sum_d(acc);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) part[(long)s * Y2_CLIP_PARTS + blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+__global__ void seg_scale_fixed_kernel(float *__restrict__ g, const long *__restrict__ seg_off, const double *__restrict__ part, float clip) {
+    const int s = blockIdx.y;
+    const long beg = seg_off[s], end = seg_off[s + 1];
+    double t = 0.0;
+    for (int b = 0; b < Y2_CLIP_PARTS; ++b) t += part[(long)s * Y2_CLIP_PARTS + b];
+    const float norm = (float)sqrt(t);
+    const float scale = clip / fmaxf(norm, clip);
+    if (scale == 1.0f) return;
+    for (long i = beg + blockIdx.x * (long)blockDim.x + threadIdx.x; i < end; i += (long)gridDim.x * blockDim.x) g[i] = g[i] * scale;
+}
 __global__ void seg_scale_kernel(float *__restrict__ g, const long *__restrict__ seg_off, const double *__restrict__ ws, float clip) {
     const int s = blockIdx.y;
     const long beg = seg_off[s], end = seg_off[s + 1];
@@ -1860,6 +1895,17 @@ extern "C" int yolo2_clip_by_norm(float *g, const long *seg_off, int nseg, float
     dim3 grid(64, nseg);
     seg_sumsq_kernel<<<grid, 256, 0, st>>>(g, seg_off, ws);
     seg_scale_kernel<<<grid, 256, 0, st>>>(g, seg_off, ws, clip);
+    Y2_CHECK_LAUNCH();
+    return YOLO2_OK;
+}
+
+extern "C" size_t yolo2_clip_fixed_workspace_bytes(int nseg) { return (size_t)(nseg > 0 ? nseg : 0) * Y2_CLIP_PARTS * sizeof(double); }
+extern "C" int yolo2_clip_by_norm_fixed(float *g, const long *seg_off, int nseg, float clip, double *ws, size_t ws_bytes, void *stream) {
+    Y2_CHECK_ARG(g && seg_off && ws && nseg > 0 && clip > 0.f && ws_bytes >= yolo2_clip_fixed_workspace_bytes(nseg));
+    hipStream_t st = (hipStream_t)stream;
+    dim3 grid(Y2_CLIP_PARTS, nseg);
+    seg_sumsq_part_kernel<<<grid, 256, 0, st>>>(g, seg_off, ws);
+    seg_scale_fixed_kernel<<<grid, 256, 0, st>>>(g, seg_off, ws, clip);
     Y2_CHECK_LAUNCH();
     return YOLO2_OK;
 }

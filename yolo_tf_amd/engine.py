@@ -110,7 +110,16 @@ class _PartPool(object):
 
 
 class Engine(object):
-    def __init__(self, graph, batch_size, dtype='bf16', training=True, seed=0, device=None, sync_bn=False, side_priority=-1):
+    def __init__(self, graph, batch_size, dtype='bf16', training=True, seed=0, device=None, sync_bn=False, side_priority=-1, deterministic=False):
+        # Deterministic training mode: every float sum of a step has ONE writer per partial and a fixed order.  Filter gradients
+        # go through yolo2_conv2d_wgrad_ws, BN statistics and BN-backward sums take the two-launch reduction passes instead of the
+        # convolution epilogues' wrapped rows, the image layer's filter gradient is not fused, the library never K-slices.  Decided per
+        # engine (no environment variable is read or written for it here), so both kinds of engine can live in one process.
+        self.deterministic = bool(deterministic) and training
+        # (the engine sees a graph, not a model family: it recognises the YOLO (v1) networks by a heuristic on their ops -- an l2-regularised layer or
+        # an un-normalised convolution with an activation; TrainSession knows the family and raises first)
+        if self.deterministic and any(op.get('l2') or (op['kind'] == 'conv' and not op['bn'] and op['act']) for op in graph.ops):
+            raise NotImplementedError('deterministic=True covers the YOLOv2 family: the YOLO (v1) fully connected head is not audited')
         if not torch.cuda.is_available():
             raise RuntimeError('yolo_tf_amd.Engine needs an MI355X (no CPU path exists)')
         ops._lib.load()
@@ -236,7 +245,7 @@ class Engine(object):
         self.pool_ymax = self.fold_finalize
         self._bind(self.graph)
         self.fold_bn = os.environ.get('YOLO2_FOLD_BN', '1') != '0'
-        self.fuse_bn_stats = os.environ.get('YOLO2_FUSE_BN_STATS', '1') != '0'
+        self.fuse_bn_stats = os.environ.get('YOLO2_FUSE_BN_STATS', '1') != '0' and not self.deterministic
         # Partial rows of the fused statistics ([2][YOLO2_BN_PART_ROWS][C] each).  Producers (convolution epilogues) need a zero buffer; the
         # consumer that finalises the rows in its own prologue only reads them and clears a buffer an EARLIER consumer is done with
         # (_PartPool below) -- no finalisation launch, no memset launch.  YOLO2_FOLD_FINALIZE=0: separate finalisation kernels (A/B).
@@ -245,7 +254,9 @@ class Engine(object):
         # image layer recomputed inside its consumers instead of stored: 'infer' (default: detect only -- batch 256: 12.5 -> 11.3 ms),
         # '1' (training too: measured neutral, the recomputing backward kernels are VALU-bound -- profiles/r03_first_layer_fused.md), '0' never
         self.fuse_first = os.environ.get('YOLO2_FUSE_FIRST', 'infer')
-        self.fuse_first_wgrad = os.environ.get('YOLO2_FUSE_FIRST_WGRAD', '1') != '0'
+        self.fuse_first_wgrad = os.environ.get('YOLO2_FUSE_FIRST_WGRAD', '1') != '0' and not self.deterministic
+        if self.deterministic and self.training:
+            self.fuse_first = 'infer'       # (the recomputing backward kernels of the image layer leave their sums in wrapped partial rows)
         self._bz_pending = {}                                    # producer layer -> (buffer, rows): BN-backward sums waiting for their apply pass
         self._fin_rows_limit = {}
         # scratch sizes come from the library's own queries (include/yolo2_hip.h yolo2_*_workspace_bytes)
@@ -273,6 +284,9 @@ class Engine(object):
             self.side_stream = torch.cuda.Stream(device=dev, priority=max(min(prio, max(lo, hi)), min(lo, hi)))
             self.overlap_wgrad = os.environ.get('YOLO2_OVERLAP_WGRAD', '1') != '0'   # 0: single stream (clean per-kernel profiles)
             self.overlap_max_m = 1 << 40   # A/B: overlap only layers with at most this many output pixels
+            self.wgrad_ws = None           # deterministic mode: slots of the split filter gradients (one buffer: they all run on one stream, in order)
+            if self.deterministic:
+                self._alloc_wgrad_ws(self.graph)
         self.img = None
 
     def _bind(self, graph):
@@ -320,7 +334,7 @@ class Engine(object):
         # BN-backward sums in the consumer's data-gradient epilogue: a batch-normalised conv whose full-resolution activation has
         # exactly one reader, a convolution writing that activation's gradient directly (no concat slice, no fan-out)
         bn_bwd_fused = {}
-        if self.training and os.environ.get('YOLO2_FUSE_BN_BWD', '1') != '0':
+        if self.training and os.environ.get('YOLO2_FUSE_BN_BWD', '1') != '0' and not self.deterministic:
             uses = {}
             for op in graph.ops:
                 for t in (op.get('inputs') or [op['x']]):
@@ -356,8 +370,34 @@ class Engine(object):
         assert names == [v.name for v in self._bindings[next(iter(self._bindings))]['graph'].variables.values()], 'different network'
         cur = self._cur
         self._bind(graph)
+        if self.deterministic:
+            self._alloc_wgrad_ws(graph)
         self._cur = cur
         self._use(*[k for k, v in self._bindings.items() if v is cur][0])
+
+    def _alloc_wgrad_ws(self, graph):
+        """Deterministic mode: one workspace for the slots of the split filter gradients, sized by the library's query for the largest layer over
+        every traced size.  One buffer serves them all: the filter gradients of a step run on ONE stream (the side stream, or the main
+        stream with YOLO2_OVERLAP_WGRAD=0), and each reduction launch has read its slots before the next producer starts."""
+        need = 0
+        for op in graph.ops:
+            if op['kind'] == 'conv':
+                x = op['x']
+                r, off, ldx = x.storage()
+                need = max(need, ops.conv2d_wgrad_workspace_bytes(self.B, x.h, x.w, op['cin'], ldx, op['cout'], pad8(op['cout']), op['ksize'], self.dtype))
+        if self.wgrad_ws is None or self.wgrad_ws.numel() * 4 < need:
+            self.wgrad_ws = torch.empty(need // 4 + 4, dtype=torch.float32, device=self.device)
+
+    def _wgrad(self, xb, dy, dW, B, h, w, cin, ldx, cout, ldy, k):
+        if self.deterministic:
+            # the one workspace is only safe while every filter gradient of a sweep runs on ONE stream: a second stream needs a buffer of its own
+            stream = torch.cuda.current_stream().cuda_stream
+            if self._wgrad_stream is None:
+                self._wgrad_stream = stream
+            assert stream == self._wgrad_stream, 'deterministic mode: filter gradients of one backward sweep on two streams share one workspace'
+            ops.conv2d_wgrad_ws(xb, dy, dW, self.wgrad_ws, B, h, w, cin, ldx, cout, ldy, k)
+        else:
+            ops.conv2d_wgrad(xb, dy, dW, B, h, w, cin, ldx, cout, ldy, k)
 
     def set_size(self, height, width):
         """Switches every following forward / backward to a bound input size; parameters, statistics and optimizer state are shared."""
@@ -497,6 +537,8 @@ class Engine(object):
         finalisation kernels, so most of the 268 MB arena is never cleared."""
         if False:        # (debugging aid: clear the whole gradient arena every step)
             return [(0, self.n_params)]
+        if self.deterministic:       # every filter gradient is stored by its reduction launch (yolo2_conv2d_wgrad_ws): nothing accumulates
+            return []
         ranges = []
         for op in self.graph.ops:
             if op['kind'] != 'conv':
@@ -530,6 +572,10 @@ class Engine(object):
 
     # ---------------------------------------------------------------- forward
     def forward(self):
+        with ops.deterministic_launches(self.deterministic):      # this thread's launch rules, for the duration of the sweep only
+            self._forward()
+
+    def _forward(self):
         self._prepare_filters()
         B = self.B
         if self.training:
@@ -666,12 +712,17 @@ class Engine(object):
         return tmp, ld, (lambda: ops.add_inplace(gb, tmp, n))
 
     def backward(self, on_layer_done=None):
+        with ops.deterministic_launches(self.deterministic):
+            self._backward(on_layer_done)
+
+    def _backward(self, on_layer_done=None):
         """Reverse sweep from the gradient already stored for the graph output (written by loss()).
         Per convolution: BN/leaky backward -> dY, then the filter gradient on the side stream overlapped with the data
         gradient (and everything after it) on the main stream: at batch 16 the 13x13 / 26x26 stages launch grids
         that cannot fill the chip on their own.  ``on_layer_done(op, event)`` is called once a layer's parameter
         gradients are enqueued; ``event`` (or None) completes when they are final."""
         B = self.B
+        self._wgrad_stream = None        # (deterministic mode: the stream this sweep's filter gradients run on, see _wgrad)
         written = set()
         reduced = set()
         inputs = set(self.graph.inputs.values())
@@ -788,14 +839,14 @@ class Engine(object):
                     ready.record(main)
                     side.wait_event(ready)
                     with torch.cuda.stream(side):
-                        ops.conv2d_wgrad(xb, dy, self.gvar[op['weights'].name], B, x.h, x.w, op['cin'], ldx, cout, ldy, k)
+                        self._wgrad(xb, dy, self.gvar[op['weights'].name], B, x.h, x.w, op['cin'], ldx, cout, ldy, k)
                         self._l2(op)
                         done = torch.cuda.Event()
                         done.record(side)
                     if ring:
                         self.dy_free[slot] = done
                 else:
-                    ops.conv2d_wgrad(xb, dy, self.gvar[op['weights'].name], B, x.h, x.w, op['cin'], ldx, cout, ldy, k)
+                    self._wgrad(xb, dy, self.gvar[op['weights'].name], B, x.h, x.w, op['cin'], ldx, cout, ldy, k)
                     self._l2(op)
                 if x not in inputs:
                     prod = self.bn_bwd_fused.get(op['name'])

@@ -87,6 +87,53 @@ def conv2d_wgrad(X, dY, dW, B, H, W, Cin, ldx, Cout, ldy, ksize):
     call('yolo2_conv2d_wgrad', ptr(X), ptr(dY), ptr(dW), B, H, W, Cin, ldx, Cout, ldy, ksize, dtype_code(X.dtype), _stream())
 
 
+def conv2d_wgrad_workspace_bytes(B, H, W, Cin, ldx, Cout, ldy, ksize, dtype):
+    """Bytes of workspace ``conv2d_wgrad_ws`` needs for this shape (0: a single pixel range, plain stores already)."""
+    return int(_lib.query('yolo2_conv2d_wgrad_workspace_bytes', B, H, W, Cin, ldx, Cout, ldy, ksize, dtype_code(dtype)))
+
+
+def conv2d_wgrad_ws(X, dY, dW, ws, B, H, W, Cin, ldx, Cout, ldy, ksize):
+    """Filter gradient without float atomics: split reductions go through ``ws`` (f32 tensor or None) and are summed in a fixed order;
+    dW is overwritten."""
+    call('yolo2_conv2d_wgrad_ws', ptr(X), ptr(dY), ptr(dW), ptr(ws), 0 if ws is None else ws.numel() * ws.element_size(), B, H, W, Cin, ldx, Cout, ldy,
+         ksize, dtype_code(X.dtype), _stream())
+
+
+def wgrad_ws_plan(B, H, W, Cin, ldx, Cout, ldy, ksize, dtype, cus):
+    """Host plan of ``conv2d_wgrad_ws`` on a device with ``cus`` compute units: dict(family, slots, slot_floats, blocks)."""
+    out = (ctypes.c_int * 4)()
+    rc = _lib.load().yolo2_debug_wgrad_ws_plan(B, H, W, Cin, ldx, Cout, ldy, ksize, dtype_code(dtype), cus, out)
+    if rc != 0:
+        raise _lib.HipKernelError('yolo2_debug_wgrad_ws_plan failed (code %d)' % rc)
+    return dict(zip(('family', 'slots', 'slot_floats', 'blocks'), list(out)))
+
+
+def set_deterministic(on):
+    """Deterministic mode of the calling thread (include/yolo2_hip.h yolo2_set_deterministic)."""
+    call('yolo2_set_deterministic', 1 if on else 0)
+
+
+class deterministic_launches(object):
+    """``with ops.deterministic_launches(on):`` -- the calling thread's launch rules are the deterministic ones inside the block (when ``on``); on exit
+    the thread's mode is what it was on entry (nested blocks, a caller that set the mode itself).  A default engine (``on`` false) never touches
+    the library's switch."""
+
+    def __init__(self, on):
+        self.on = bool(on)
+        self.prev = 0
+
+    def __enter__(self):
+        if self.on:
+            self.prev = int(_lib.query('yolo2_get_deterministic'))
+            if not self.prev:
+                set_deterministic(True)
+
+    def __exit__(self, *exc):
+        if self.on and not self.prev:
+            set_deterministic(False)
+        return False
+
+
 def filter_prep(Wt, Ffwd, Fdgr, ksize, Cin, ldcin, Cout, ldcout, dtype):
     call('yolo2_filter_prep', ptr(Wt), ptr(Ffwd), ptr(Fdgr), ksize, Cin, ldcin, Cout, ldcout, dtype_code(dtype), _stream())
 
@@ -336,6 +383,11 @@ def workspace_bytes(kind, *args):
 
 def clip_by_norm(g, seg_off, nseg, clip, ws):
     call('yolo2_clip_by_norm', ptr(g), ptr(seg_off), nseg, clip, ptr(ws), _stream())
+
+
+def clip_by_norm_fixed(g, seg_off, nseg, clip, ws):
+    """Per-tensor clip with fixed-order sums of squares (deterministic mode); ws: f64 tensor of ``workspace_bytes('clip_fixed', nseg)`` bytes."""
+    call('yolo2_clip_by_norm_fixed', ptr(g), ptr(seg_off), nseg, clip, ptr(ws), ws.numel() * ws.element_size(), _stream())
 
 
 def selftest_tr16():

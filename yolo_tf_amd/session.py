@@ -25,9 +25,14 @@ class TrainSession(object):
 
     def __init__(self, builder, batch_size, dtype='bf16', optimizer='adam', learning_rate=1e-6, gradient_clip=0.0,
                  config=None, seed=0, world_size=1, bucket_mb=64.0, preprocess_mode=0, sizes=None, grad_dtype='f32', comm_cus=None, comm_timing=False,
-                 sync_bn=False, shard_optimizer=False):
+                 sync_bn=False, shard_optimizer=False, deterministic=None):
         """``sizes``: optional list of (width, height) input sizes for multi-scale training (BASELINE configs[3]); buffers are
-        allocated once for the largest, ``set_size`` switches between them, the builder's configured size is selected first."""
+        allocated once for the largest, ``set_size`` switches between them, the builder's configured size is selected first.
+
+        ``deterministic``: bitwise reproducible steps (deterministic training mode) -- same parameters, optimizer slots, BN state,
+        global_step, image tensor and labels => bitwise the same state after ``step()``, whatever the buffer addresses, the process or the
+        run.  None (default): on when ``[mi355x] deterministic`` of the config is true or YOLO2_DETERMINISTIC=1 is set; False / True decide here.  YOLOv2
+        family only; with world_size > 1 the local computation is deterministic but nothing is promised across the collective."""
         assert builder.training, 'call builder(data, training=True) first'
         self.builder = builder
         self.B = batch_size
@@ -41,8 +46,19 @@ class TrainSession(object):
                 traced[wh] = builder.trace(wh[0], wh[1], training=True)
         largest = max(traced, key=lambda wh: wh[0] * wh[1])
         assert all(w <= largest[0] and h <= largest[1] for w, h in traced), 'one size must contain all the others'
+        if deterministic is None:
+            cfg = config if config is not None else getattr(builder, 'config', None)
+            deterministic = (cfg is not None and cfg.has_option('mi355x', 'deterministic') and cfg.getboolean('mi355x', 'deterministic')) or \
+                os.environ.get('YOLO2_DETERMINISTIC', '0') == '1'
+        self.deterministic = bool(deterministic)
+        if self.deterministic and self.v1:
+            raise NotImplementedError('deterministic=True covers the YOLOv2 family: the YOLO (v1) loss and fully connected head still sum in arrival order')
+        if self.deterministic and world_size > 1:
+            import logging
+            logging.getLogger(__name__).warning('deterministic=True with world_size = %d: each replica computes its gradients in a fixed order, '
+                                                'but no bitwise promise is made across the gradient collective', world_size)
         self.engine = Engine(traced[largest][0], batch_size, dtype, training=True, seed=seed, sync_bn=sync_bn and world_size > 1,
-                             side_priority=-1 if world_size == 1 else 0)
+                             side_priority=-1 if world_size == 1 else 0, deterministic=self.deterministic)
         e = self.engine
         if e.sync_bn:                # batch moments and BN-backward sums over all replicas ([mi355x] sync_bn; default: replica-local like N reference processes)
             import torch.distributed as dist
@@ -67,7 +83,7 @@ class TrainSession(object):
         self.optimizer = Optimizer(optimizer, config if config is not None else builder.config, e.n_params, dev)
         self.lr_fn = learning_rate_fn(config if config is not None else builder.config, learning_rate)
         self.gradient_clip = float(gradient_clip)
-        self.clip_ws = torch.zeros(ops.workspace_bytes('clip', e.n_seg) // 8, dtype=torch.float64, device=dev)
+        self.clip_ws = torch.zeros(ops.workspace_bytes('clip_fixed' if self.deterministic else 'clip', e.n_seg) // 8, dtype=torch.float64, device=dev)
         self.global_step = 0
         self.world_size = world_size
         self.preprocess_mode = preprocess_mode
@@ -99,7 +115,7 @@ class TrainSession(object):
         # step; the 13x13 layers whose gradients come first hold 84 % of the parameters).  Bit-identical to the one-launch form (same kernel per
         # layer, tests/test_network_gpu.py).  Measured SLOWER: 3.72 vs 3.62 ms per step (profiles/r05_early_adam.txt) -- the update's thousands
         # of small workgroups (16.6 KB of LDS each) occupy CUs that the 150 KB convolution workgroups then cannot be placed on.
-        self.early_adam = (os.environ.get('YOLO2_EARLY_ADAM', '0') == '1' and world_size == 1 and optimizer == 'adam' and self.fuse_adam_prep
+        self.early_adam = (os.environ.get('YOLO2_EARLY_ADAM', '0') == '1' and not self.deterministic and world_size == 1 and optimizer == 'adam' and self.fuse_adam_prep
                            and self.gradient_clip <= 0 and not getattr(e, '_has_l2', False) and dev.type == 'cuda')
         self.opt_stream = torch.cuda.Stream(device=dev) if self.early_adam else None
         self._early_pending = False
@@ -179,7 +195,10 @@ class TrainSession(object):
             # [TF-sem] clip happens on the (averaged) gradient: scale first when data-parallel
             if self.world_size > 1:
                 ops.scale(e.grads, e.n_params, 1.0 / self.world_size)
-            ops.clip_by_norm(e.grads, e.seg_off, e.n_seg, self.gradient_clip, self.clip_ws)
+            if self.deterministic:      # fixed-order sums of squares (64 stored partials per tensor) instead of f64 atomics
+                ops.clip_by_norm_fixed(e.grads, e.seg_off, e.n_seg, self.gradient_clip, self.clip_ws)
+            else:
+                ops.clip_by_norm(e.grads, e.seg_off, e.n_seg, self.gradient_clip, self.clip_ws)
             gscale = 1.0
         else:
             gscale = 1.0 / self.world_size
