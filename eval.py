@@ -1,0 +1,107 @@
+#!/usr/bin/env python
+"""eval.py -- mean average precision of a checkpoint on MI355X (PASCAL VOC protocol; new work, the reference has no evaluator):
+
+    python eval.py -c config.ini config/yolo2/darknet-20.ini -p val -b 64 -t 0.005 --threshold_iou 0.45 --iou 0.5 --mode all --json out.json
+
+The dataset sits in HBM; resize, forward (moving-average BN), decode, NMS, matching against the ground truth, the per-class sort and
+both VOC metrics (11-point `voc07`, area `voc12`) run on the GPU.  Restores the latest checkpoint of utils.get_logdir(config) exactly
+as detect.py does.  ``--data cache`` reads the ``-p`` profiles of the reference's TFRecord cache (which has no `difficult` flag: every
+box counts), ``--data file.npz`` the raw-object layout train.py accepts plus an optional ``objects_difficult``, ``--data synthetic`` a
+seeded generator.  Images are resized by the device's TF-style bilinear kernel, as in training -- not by PIL as in detect.py.
+Import-safe."""
+import argparse
+import configparser
+import json
+import logging
+import os
+
+from yolo_tf_amd import utils
+
+PREPROCESS = {'std': 0, 'darknet': 1}
+
+
+def load_data(args, config, classes):
+    """(images, objects, difficult or None) of the chosen source."""
+    from yolo_tf_amd import evaluate
+    if args.data == 'synthetic':
+        return evaluate.synthetic_dataset(args.images, classes, seed=args.seed)
+    if args.data == 'cache':
+        from yolo_tf_amd.utils import tfrecord
+        cachedir = utils.get_cachedir(config)
+        paths = [os.path.join(cachedir, profile + '.tfrecord') for profile in args.profile]
+        logging.info('loading ' + ', '.join(paths))
+        images, objects = tfrecord.load_dataset(paths, limit=args.limit)
+        return images, objects, None
+    images, objects, difficult = evaluate.load_npz(os.path.expanduser(os.path.expandvars(args.data)))
+    if args.limit is not None:
+        images, objects, difficult = images[:args.limit], objects[:args.limit], difficult[:args.limit]
+    return images, objects, difficult
+
+
+def main():
+    from yolo_tf_amd import checkpoint, evaluate, tf_checkpoint
+    from yolo_tf_amd.session import DetectSession
+    model = config.get('config', 'model')
+    yolo = __import__('yolo_tf_amd.model.' + model, fromlist=['Builder'])
+    utils.ensure_names(config)
+    builder = yolo.Builder(args, config)
+    builder(None)
+    dtype = args.dtype or (config.get('mi355x', 'dtype') if config.has_option('mi355x', 'dtype') else 'bf16')
+    sess = DetectSession(builder, args.batch_size, dtype=dtype)
+    logdir = utils.get_logdir(config)
+    model_path = checkpoint.latest_checkpoint(logdir)
+    tf_path = None if model_path else tf_checkpoint.latest_checkpoint(logdir)
+    if model_path is None and tf_path is None:
+        raise FileNotFoundError('no checkpoint in ' + logdir)
+    logging.info('load ' + (model_path or tf_path))
+    step = checkpoint.restore(model_path, engine=sess.engine) if model_path else tf_checkpoint.restore(tf_path, engine=sess.engine)
+    logging.info('global_step=%d' % step)
+    images, objects, difficult = load_data(args, config, len(builder.names))
+    m = sess.model
+    data = evaluate.EvalData(images, objects, args.batch_size, builder.width, builder.height, m.cell_width, m.cell_height, difficult=difficult)
+    result = evaluate.evaluate(builder, sess, data, mode=args.mode, threshold=args.threshold, threshold_iou=args.threshold_iou, iou=args.iou,
+                               preprocess_mode=PREPROCESS[args.preprocess], max_records=args.max_records)
+    print('%-16s %8s %8s %6s %6s %8s' % ('class', 'ap07', 'ap12', 'npos', 'tp', 'fp'))
+    for i, name in enumerate(builder.names):
+        print('%-16s %8.4f %8.4f %6d %6d %8d' % (name, result['ap07'][i], result['ap12'][i], result['npos'][i], result['tp'][i], result['fp'][i]))
+    print('mAP07 %.4f' % result['mAP07'])
+    print('mAP12 %.4f' % result['mAP12'])
+    if args.json:
+        out = dict(result, names=list(builder.names), images=len(images), checkpoint=model_path or tf_path, global_step=int(step),
+                   config={k: getattr(args, k) for k in ('config', 'profile', 'data', 'batch_size', 'threshold', 'threshold_iou', 'iou', 'mode',
+                                                         'preprocess', 'dtype', 'limit', 'images', 'seed')})
+        with open(os.path.expanduser(os.path.expandvars(args.json)), 'w') as f:
+            json.dump(out, f, indent=1)          # (NaN of a class without ground truth is written as NaN, which Python's json reads back)
+    return result
+
+
+def make_args(argv=None):
+    parser = argparse.ArgumentParser(description='VOC mean average precision of the latest checkpoint, evaluated on the GPU')
+    parser.add_argument('-c', '--config', nargs='+', default=['config.ini'], help='config file')
+    parser.add_argument('-p', '--profile', nargs='+', default=['val'], help='dataset profiles of the cache (--data cache)')
+    parser.add_argument('--data', default='cache', help="'cache' (the reference's TFRecord cache), 'synthetic' or a .npz file with raw objects")
+    parser.add_argument('-b', '--batch_size', type=int, default=64)
+    parser.add_argument('-t', '--threshold', type=float, default=0.005, help='score threshold of a detection')
+    parser.add_argument('--threshold_iou', type=float, default=0.45, help='IoU threshold of the NMS')
+    parser.add_argument('--iou', type=float, default=0.5, help='IoU a detection needs (strictly above) to match a ground truth box')
+    parser.add_argument('--mode', default='detect', choices=['detect', 'all'],
+                        help="'detect': one detection per box, its arg-max class (detect.py); 'all': one per (box, class) (Darknet valid)")
+    parser.add_argument('--preprocess', default='std', choices=sorted(PREPROCESS), help='the preprocess function')
+    parser.add_argument('--json', help='write the result, the configuration, the checkpoint path and the global step here')
+    parser.add_argument('--limit', type=int, default=None, help='evaluate only the first images')
+    parser.add_argument('--images', type=int, default=32, help='--data synthetic: number of images')
+    parser.add_argument('--seed', type=int, default=0, help='--data synthetic: seed')
+    parser.add_argument('--max_records', type=int, default=None, help='capacity of the record buffer (default: the worst case of the mode)')
+    parser.add_argument('--dtype', default=None, choices=['bf16', 'f32'])
+    parser.add_argument('--level', default='info', help='logging level')
+    return parser.parse_args(argv)
+
+
+if __name__ == '__main__':
+    args = make_args()
+    config = configparser.ConfigParser()
+    utils.load_config(config, args.config)
+    logging.basicConfig()
+    if args.level:
+        logging.getLogger().setLevel(args.level.upper())
+    main()

@@ -554,6 +554,61 @@ int yolo2_cast_bf16_f32(const void *src, float *dst, long n, void *stream);
  * *started counts the resident ones (what a collective's persistent kernels look like to the dispatcher) */
 int yolo2_debug_occupy(int workgroups, int *stop, int *started, int max_us, void *stream);
 
+/* ---- evaluation: PASCAL VOC average precision of the detections a batch leaves on the device (new work: the reference has no
+ * evaluator).  COCO's protocol (101 points, IoU 0.5:0.95, area ranges, best UNMATCHED candidate) is not implemented.
+ *
+ * Stage A, yolo2_eval_collect, once per detect batch; no host synchronisation, no copy to the host.
+ *   conf [B,N,C] f32 after NMS (zeros where suppressed), xy_min / xy_max [B,N,2] f32 in cell units.  Ground truth: gt_class [G] int,
+ *   gt_box [G,4] f32 (xmin, ymin, xmax, ymax) IN THE SAME CELL UNITS (no coordinate transform happens here), gt_difficult [G] bytes,
+ *   gt_first [B+1] CSR offsets per image (at most YOLO2_EVAL_MAX_GT_PER_IMAGE boxes in one image).  All device pointers, non-null even
+ *   when G == 0.  image_base = dataset index of the batch's first image; images b >= n_valid are padding: no records, no npos.
+ *   Detections: YOLO2_EVAL_MODE_DETECT = one per box, class = FIRST arg-max of conf[i,:], score = that value, kept if score > threshold
+ *   (what detect.py prints); YOLO2_EVAL_MODE_ALL = one per (box, class) with conf[i,c] > threshold (what Darknet's `valid` emits).  NaN
+ *   scores make no detection.
+ *   Matching (VOC devkit), independent per (image, class): detections are visited in (score descending, box index ascending) order; the
+ *   candidate is the ground truth of the same image and class with the highest IoU, ties to the lowest index, already matched boxes
+ *   included; IoU is f32 in the reference's operation order, (a1+a2)-inter with floor 1e-10 (utils/postprocess.py:21-36).
+ *   iou > iou_threshold (strict) and candidate difficult: IGNORED; iou > iou_threshold and candidate not yet matched: TP, the candidate
+ *   becomes matched; iou > iou_threshold and candidate matched: FP (duplicate); otherwise FP.
+ *   Output: yolo2_eval_record entries appended to `records` (capacity max_records) in (image, box, class) order, at positions that come
+ *   from counts and prefix sums only (two runs give bitwise equal buffers), and npos[C] += non-difficult ground truth per class.
+ *   state: YOLO2_EVAL_STATE_WORDS 8-byte words the caller zeroes before the first collect: [0] records wanted so far, [1] error bits.
+ *   Nothing is ever written at or past records[max_records]; word 0 keeps counting, and yolo2_eval_finalize reports both numbers.
+ *   ws: yolo2_eval_collect_workspace_bytes(B).
+ * Stage B, yolo2_eval_finalize, once per evaluation; reads the record count from `state` on the device (no synchronisation).
+ *   Sorts the non-ignored records per class by (score descending, image index ascending, box index ascending) -- a radix sort on the
+ *   device over box (< N), image (< n_images), score bits and class -- and integrates: inclusive counts of TP and FP along that order,
+ *   recall = tp / npos, precision = tp / (tp + fp) in f64; ap07 = mean over t = k/10, k = 0..10 of the highest precision among points
+ *   with recall >= t (0 if none); ap12 = area under the monotone precision envelope, summed where recall changes.  npos == 0: both NaN;
+ *   npos > 0 and no detections: 0.
+ *   results: yolo2_eval_result_bytes(C) bytes of 8-byte words: ap07 [C] f64, ap12 [C] f64, then int64 npos [C], tp [C], fp [C],
+ *   ignored [C], records held, records wanted (> max_records: the buffer was too small and every other number is void), error bits
+ *   (1: ground truth class outside [0,C); 2: gt_first not ascending within [0,G] or too many boxes in an image; 4: a record's image, box
+ *   or class outside n_images, N, C).  Optional (may be NULL): sorted_records [max_records] (class-major, ignored records last),
+ *   cum_tp / cum_fp [max_records] int = the inclusive counts per class along the sorted order.
+ *   ws: yolo2_eval_workspace_bytes(max_records, C) = two record buffers + the digit table of the sort, each rounded up to 256 bytes. */
+enum { YOLO2_EVAL_MODE_DETECT = 0, YOLO2_EVAL_MODE_ALL = 1 };
+enum { YOLO2_EVAL_FP = 0, YOLO2_EVAL_TP = 1, YOLO2_EVAL_IGNORED = 2 };
+#define YOLO2_EVAL_MAX_GT_PER_IMAGE 512
+#define YOLO2_EVAL_MAX_CLASSES (1 << 20)
+#define YOLO2_EVAL_STATE_WORDS 2
+typedef struct {
+    float score;
+    int image;                 /* dataset index */
+    int box;                   /* index into the N boxes of the image */
+    unsigned class_flag;       /* class << 2 | YOLO2_EVAL_FP / _TP / _IGNORED */
+} yolo2_eval_record;
+size_t yolo2_eval_record_bytes(long max_records);                 /* 16 * max_records */
+size_t yolo2_eval_collect_workspace_bytes(int B);                 /* 4 * B */
+size_t yolo2_eval_workspace_bytes(long max_records, int C);
+size_t yolo2_eval_result_bytes(int C);                            /* 8 * (6 C + 3) */
+int yolo2_eval_collect(const float *conf, const float *xy_min, const float *xy_max, const int *gt_class, const float *gt_box,
+                       const unsigned char *gt_difficult, const int *gt_first, int G, int B, int N, int C, int n_valid, int image_base,
+                       int mode, float threshold, float iou_threshold, void *records, long max_records, unsigned long long *state,
+                       int *npos, int *ws, void *stream);
+int yolo2_eval_finalize(const void *records, long max_records, unsigned long long *state, const int *npos, int C, int n_images, int N,
+                        void *ws, size_t ws_bytes, void *results, void *sorted_records, int *cum_tp, int *cum_fp, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

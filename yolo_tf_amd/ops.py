@@ -556,3 +556,21 @@ def cast_bf16_f32(src, dst, n):
 
 def debug_occupy(workgroups, stop, started, max_us):
     call('yolo2_debug_occupy', workgroups, ptr(stop), ptr(started), max_us, _stream())
+
+
+EVAL_MODES = {'detect': 0, 'all': 1}       # YOLO2_EVAL_MODE_* (include/yolo2_hip.h)
+EVAL_RECORD_BYTES = 16                     # sizeof(yolo2_eval_record): score f32, image i32, box i32, class << 2 | flag
+EVAL_STATE_WORDS = 2                       # YOLO2_EVAL_STATE_WORDS
+
+
+def eval_collect(conf, xy_min, xy_max, gt_class, gt_box, gt_difficult, gt_first, G, B, N, C, n_valid, image_base, mode, threshold, iou_threshold,
+                 records, max_records, state, npos, ws):
+    """Stage A of the evaluator (yolo2_eval_collect): appends this batch's detection records and ground truth counts; asynchronous."""
+    call('yolo2_eval_collect', ptr(conf), ptr(xy_min), ptr(xy_max), ptr(gt_class), ptr(gt_box), ptr(gt_difficult), ptr(gt_first), G, B, N, C,
+         n_valid, image_base, mode, threshold, iou_threshold, ptr(records), max_records, ptr(state), ptr(npos), ptr(ws), _stream())
+
+
+def eval_finalize(records, max_records, state, npos, C, n_images, N, ws, results, sorted_records=None, cum_tp=None, cum_fp=None):
+    """Stage B of the evaluator (yolo2_eval_finalize): device sort per class + both VOC average precisions into ``results``; asynchronous."""
+    call('yolo2_eval_finalize', ptr(records), max_records, ptr(state), ptr(npos), C, n_images, N, ptr(ws), ws.numel() * ws.element_size(),
+         ptr(results), ptr(sorted_records), ptr(cum_tp), ptr(cum_fp), _stream())
