@@ -1,13 +1,17 @@
 #!/usr/bin/env python
-"""eval.py -- mean average precision of a checkpoint on MI355X (PASCAL VOC protocol; new work, the reference has no evaluator):
+"""eval.py -- mean average precision of a checkpoint on MI355X (PASCAL VOC or COCO protocol; new work, the reference has no evaluator):
 
     python eval.py -c config.ini config/yolo2/darknet-20.ini -p val -b 64 -t 0.005 --threshold_iou 0.45 --iou 0.5 --mode all --json out.json
+    python eval.py -c config.ini config/yolo2/darknet-80.ini -p val -b 64 -t 0.005 --mode all --protocol coco --json out.json
 
 The dataset sits in HBM; resize, forward (moving-average BN), decode, NMS, matching against the ground truth, the per-class sort and
 both VOC metrics (11-point `voc07`, area `voc12`) run on the GPU.  Restores the latest checkpoint of utils.get_logdir(config) exactly
 as detect.py does.  ``--data cache`` reads the ``-p`` profiles of the reference's TFRecord cache (which has no `difficult` flag: every
 box counts), ``--data file.npz`` the raw-object layout train.py accepts plus an optional ``objects_difficult``, ``--data synthetic`` a
 seeded generator.  Images are resized by the device's TF-style bilinear kernel, as in training -- not by PIL as in detect.py.
+``--protocol coco`` prints COCO's twelve numbers (AP@[.5:.95], AP50, AP75, AP by area, AR by detection limit and by area) instead.  A
+.npz file may bring ``objects_crowd`` and ``objects_area``; the reference's cache has no crowd flag (utils/data/cache.py:127 reads
+crowd annotations as ordinary boxes), so with ``--data cache`` every box counts and its area is its box area.
 Import-safe."""
 import argparse
 import configparser
@@ -21,21 +25,21 @@ PREPROCESS = {'std': 0, 'darknet': 1}
 
 
 def load_data(args, config, classes):
-    """(images, objects, difficult or None) of the chosen source."""
+    """(images, objects, difficult or None, crowd or None, area or None) of the chosen source."""
     from yolo_tf_amd import evaluate
     if args.data == 'synthetic':
-        return evaluate.synthetic_dataset(args.images, classes, seed=args.seed)
+        return evaluate.synthetic_dataset(args.images, classes, seed=args.seed) + (None, None)
     if args.data == 'cache':
         from yolo_tf_amd.utils import tfrecord
         cachedir = utils.get_cachedir(config)
         paths = [os.path.join(cachedir, profile + '.tfrecord') for profile in args.profile]
         logging.info('loading ' + ', '.join(paths))
         images, objects = tfrecord.load_dataset(paths, limit=args.limit)
-        return images, objects, None
-    images, objects, difficult = evaluate.load_npz(os.path.expanduser(os.path.expandvars(args.data)))
+        return images, objects, None, None, None
+    fields = evaluate.load_npz(os.path.expanduser(os.path.expandvars(args.data)), coco=True)
     if args.limit is not None:
-        images, objects, difficult = images[:args.limit], objects[:args.limit], difficult[:args.limit]
-    return images, objects, difficult
+        fields = tuple(f if f is None else f[:args.limit] for f in fields)
+    return fields
 
 
 def main():
@@ -56,20 +60,31 @@ def main():
     logging.info('load ' + (model_path or tf_path))
     step = checkpoint.restore(model_path, engine=sess.engine) if model_path else tf_checkpoint.restore(tf_path, engine=sess.engine)
     logging.info('global_step=%d' % step)
-    images, objects, difficult = load_data(args, config, len(builder.names))
+    images, objects, difficult, crowd, area = load_data(args, config, len(builder.names))
     m = sess.model
-    data = evaluate.EvalData(images, objects, args.batch_size, builder.width, builder.height, m.cell_width, m.cell_height, difficult=difficult)
+    data = evaluate.EvalData(images, objects, args.batch_size, builder.width, builder.height, m.cell_width, m.cell_height, difficult=difficult,
+                             crowd=crowd, area=area)
     result = evaluate.evaluate(builder, sess, data, mode=args.mode, threshold=args.threshold, threshold_iou=args.threshold_iou, iou=args.iou,
-                               preprocess_mode=PREPROCESS[args.preprocess], max_records=args.max_records)
+                               preprocess_mode=PREPROCESS[args.preprocess], max_records=args.max_records, protocol=args.protocol)
+    extra = dict(names=list(builder.names), images=len(images), checkpoint=model_path or tf_path, global_step=int(step),
+                 config={k: getattr(args, k) for k in ('config', 'profile', 'data', 'batch_size', 'threshold', 'threshold_iou', 'iou', 'mode', 'protocol',
+                                                       'preprocess', 'dtype', 'limit', 'images', 'seed')})
+    if args.protocol == 'coco':
+        for name, v in zip(evaluate.COCO_STAT_NAMES, result['stats']):
+            print('%s = %0.3f' % (name, v))
+        if args.json:
+            out = dict(extra, stats=result['stats'], stat_names=[n.strip() for n in evaluate.COCO_STAT_NAMES], detections=result['detections'],
+                       **{k: result[k].tolist() for k in ('ap', 'recall', 'npig')})
+            with open(os.path.expanduser(os.path.expandvars(args.json)), 'w') as f:
+                json.dump(out, f, indent=1)
+        return result
     print('%-16s %8s %8s %6s %6s %8s' % ('class', 'ap07', 'ap12', 'npos', 'tp', 'fp'))
     for i, name in enumerate(builder.names):
         print('%-16s %8.4f %8.4f %6d %6d %8d' % (name, result['ap07'][i], result['ap12'][i], result['npos'][i], result['tp'][i], result['fp'][i]))
     print('mAP07 %.4f' % result['mAP07'])
     print('mAP12 %.4f' % result['mAP12'])
     if args.json:
-        out = dict(result, names=list(builder.names), images=len(images), checkpoint=model_path or tf_path, global_step=int(step),
-                   config={k: getattr(args, k) for k in ('config', 'profile', 'data', 'batch_size', 'threshold', 'threshold_iou', 'iou', 'mode',
-                                                         'preprocess', 'dtype', 'limit', 'images', 'seed')})
+        out = dict(result, **extra)
         with open(os.path.expanduser(os.path.expandvars(args.json)), 'w') as f:
             json.dump(out, f, indent=1)          # (NaN of a class without ground truth is written as NaN, which Python's json reads back)
     return result
@@ -86,6 +101,10 @@ def make_args(argv=None):
     parser.add_argument('--iou', type=float, default=0.5, help='IoU a detection needs (strictly above) to match a ground truth box')
     parser.add_argument('--mode', default='detect', choices=['detect', 'all'],
                         help="'detect': one detection per box, its arg-max class (detect.py); 'all': one per (box, class) (Darknet valid)")
+    parser.add_argument('--protocol', default='voc', choices=['voc', 'coco'],
+                        help="'voc': the two PASCAL VOC average precisions at --iou; 'coco': COCO's twelve numbers (IoU .5:.95, area ranges, "
+                             "detection limits 1 / 10 / 100; --iou is unused).  With --data cache no box is crowd: the reference's cache reads crowd "
+                             "annotations as ordinary boxes")
     parser.add_argument('--preprocess', default='std', choices=sorted(PREPROCESS), help='the preprocess function')
     parser.add_argument('--json', help='write the result, the configuration, the checkpoint path and the global step here')
     parser.add_argument('--limit', type=int, default=None, help='evaluate only the first images')

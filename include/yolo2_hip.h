@@ -555,7 +555,7 @@ int yolo2_cast_bf16_f32(const void *src, float *dst, long n, void *stream);
 int yolo2_debug_occupy(int workgroups, int *stop, int *started, int max_us, void *stream);
 
 /* ---- evaluation: PASCAL VOC average precision of the detections a batch leaves on the device (new work: the reference has no
- * evaluator).  COCO's protocol (101 points, IoU 0.5:0.95, area ranges, best UNMATCHED candidate) is not implemented.
+ * evaluator).  COCO's protocol has its own section and entry points below ("evaluation, COCO protocol").
  *
  * Stage A, yolo2_eval_collect, once per detect batch; no host synchronisation, no copy to the host.
  *   conf [B,N,C] f32 after NMS (zeros where suppressed), xy_min / xy_max [B,N,2] f32 in cell units.  Ground truth: gt_class [G] int,
@@ -608,6 +608,73 @@ int yolo2_eval_collect(const float *conf, const float *xy_min, const float *xy_m
                        int *npos, int *ws, void *stream);
 int yolo2_eval_finalize(const void *records, long max_records, unsigned long long *state, const int *npos, int C, int n_images, int N,
                         void *ws, size_t ws_bytes, void *results, void *sorted_records, int *cum_tp, int *cum_fp, void *stream);
+
+/* ---- evaluation, COCO protocol: pycocotools' COCOeval for iouType 'bbox', restated (new work).  AP / AR over IoU thresholds, area
+ * ranges and detection limits.  Two deviations from pycocotools, both deliberate: IoU is f32 (the IoU of the section above; pycocotools
+ * uses f64), so that a comparison at a threshold gives the same answer on the device and in the checker bit for bit; and `area` of a
+ * ground truth box is whatever the caller passes (the pixel area of the box unless it knows the segmentation's).
+ *
+ * Detections are formed exactly as in the section above (modes, strict > threshold, NaN, -0 -> +0).  Inside one (image, class) they are
+ * ordered by score descending, then box index ascending; the position in that order is the RANK.  Only ranks < max_dets (at most
+ * YOLO2_EVAL_COCO_MAX_DETS) produce a record.
+ * Ground truth: gt_class [G], gt_box [G,4] in cell units, gt_area [G] f32 in source-image pixels, gt_flags [G] bytes: bit 0 = ignore,
+ * bit 1 = crowd (crowd implies ignore: either bit ignores).  Under area range [lo, hi] a box is IGNORED when a flag bit is set, or
+ * area < lo, or area > hi.
+ * Tables come from the HOST (read during the call, passed to the kernels by value): area_ranges [A][2] f32 (A <= 4), iou_thresholds
+ * [T] f32 (T <= 10), recall_thresholds [R] f64 (R <= 101, ascending), slices [S][2] int = (area range index, detection limit <=
+ * max_dets), S <= 8.  None may be NaN.
+ * scale [B,2] f32 = source pixels per cell (x, y) of each image.  A detection's area is ((xmax-xmin)*scale_x) * ((ymax-ymin)*scale_y)
+ * in f32, contraction off.
+ * IoU against a non-crowd box: that f32 IoU.  Against a crowd box: inter / fmaxf((xmax-xmin)*(ymax-ymin) of the detection, 1e-10f), f32.
+ * Matching, per (image, class, area range a, IoU threshold t), detections in rank order.  The class's boxes are scanned non-ignored
+ * (under a) first, then ignored, each group in index order.  Per detection: best = min((double)t, 1 - 1e-10), m = none; for each box g
+ * in scan order: skip g if it is matched at (a, t) and not crowd; STOP if m is set, m is not ignored and g is ignored; skip g if
+ * (double)iou(d, g) < best; otherwise best = iou, m = g (>=: of equal overlaps the LAST in scan order wins; iou == t matches).  If m is
+ * set the detection is MATCHED, it is IGNORED exactly when m is ignored, and m becomes matched (a crowd box can be taken again).  An
+ * unmatched detection is ignored when its own area is < lo or > hi.  The outcome for the first k detections does not depend on later
+ * ones, so matching runs once with max_dets and smaller detection limits are rank filters.
+ * Record (40 bytes): score, image, box, class, rank, and two bit sets: bit a * T + t of `matched` / `ignored`.  Records are appended in
+ * (image, class, rank) order at positions that come from counts and prefix sums only.  npig [A][C] int (caller zeroes it) += the boxes
+ * of the class not ignored under range a.  state, capacity and overflow: as in the section above (nothing is written at or past
+ * records[max_records], word 0 keeps counting, finalize reports both).  ws: yolo2_eval_coco_collect_workspace_bytes(B, N, C).
+ * C <= YOLO2_EVAL_COCO_MAX_CLASSES.  Box coordinates must be finite: overlaps of NaN boxes follow fminf / fmaxf and are no part of
+ * the rules.
+ * Finalize: sorts by (class, score descending, image ascending, rank ascending) and, per class k, slice s = (a, limit), threshold t:
+ * takes the records with rank < limit in that order, drops those ignored at (a, t); npig == 0: ap = recall = -1; otherwise cumulative
+ * tp / fp, rc = tp / npig, pr = tp / ((fp + tp) + 2.220446049250313e-16) in f64; recall[s,t,k] = last rc (0 without records); pr is
+ * made non-increasing from the back (reverse running maximum); q[r] = pr at the first index with rc >= recall_thresholds[r], 0 if
+ * none; ap[s,t,k] = (q[0] + ... + q[R-1], added in index order) / R.
+ * results: yolo2_eval_coco_result_bytes(S, T, A, C) bytes of 8-byte words: ap [S][T][C] f64, recall [S][T][C] f64, npig [A][C] int64,
+ * records held, records wanted, error bits (as above; 4 also covers a rank >= max_dets).
+ * ws of finalize: yolo2_eval_coco_workspace_bytes(max_records, C) = two buffers of 16-byte sort keys + the digit table. */
+#define YOLO2_EVAL_COCO_MAX_AREAS 4
+#define YOLO2_EVAL_COCO_MAX_IOUS 10
+#define YOLO2_EVAL_COCO_MAX_RECALLS 101
+#define YOLO2_EVAL_COCO_MAX_SLICES 8
+#define YOLO2_EVAL_COCO_MAX_DETS 128
+#define YOLO2_EVAL_COCO_MAX_CLASSES 1024
+typedef struct {
+    float score;
+    int image;                 /* dataset index */
+    int box;                   /* index into the N boxes of the image */
+    int cls;
+    int rank;                  /* position among the detections of its (image, class) */
+    unsigned reserved;         /* 0 */
+    unsigned long long matched;    /* bit a * T + t */
+    unsigned long long ignored;    /* bit a * T + t */
+} yolo2_eval_coco_record;
+size_t yolo2_eval_coco_record_bytes(long max_records);            /* 40 * max_records */
+size_t yolo2_eval_coco_collect_workspace_bytes(int B, int N, int C);
+size_t yolo2_eval_coco_workspace_bytes(long max_records, int C);
+size_t yolo2_eval_coco_result_bytes(int S, int T, int A, int C);  /* 8 * (2 S T C + A C + 3) */
+int yolo2_eval_coco_collect(const float *conf, const float *xy_min, const float *xy_max, const int *gt_class, const float *gt_box,
+                            const float *gt_area, const unsigned char *gt_flags, const int *gt_first, const float *scale, int G, int B,
+                            int N, int C, int n_valid, int image_base, int mode, float threshold, const float *area_ranges, int A,
+                            const float *iou_thresholds, int T, int max_dets, void *records, long max_records,
+                            unsigned long long *state, int *npig, void *ws, size_t ws_bytes, void *stream);
+int yolo2_eval_coco_finalize(const void *records, long max_records, unsigned long long *state, const int *npig, int C, int n_images, int N,
+                             int A, int T, int max_dets, const int *slices, int S, const double *recall_thresholds, int R, void *ws,
+                             size_t ws_bytes, void *results, void *stream);
 
 #ifdef __cplusplus
 }

@@ -2,12 +2,14 @@
 does not cover this).  One process, HIP events after warm-up:
 
   1. DetectSession.detect per batch at batch 64 and 256 (Darknet-19, 416x416, VOC-20, bf16) and its NMS launch alone: the baseline;
-  2. Evaluator.add per batch on the same batches, both modes, and the host time spent inside add;
+  2. Evaluator.add per batch on the same batches, both modes, and the host time spent inside add; the same for CocoEvaluator.add
+     and for CocoEvaluator.result() on the records of those adds (profiles/eval_coco.md);
   3. Evaluator.result() (the sort and the AP) for M near 1e5 and M = 4952 x 845 synthetic records;
   4. the NumPy checker (tests/eval_ref.py) on the same records, wall time.
 
 ``--trace`` instead runs one small evaluation whose window between the first add and result() is bracketed by two back-to-back device
-synchronisations, for `rocprofv3 --hip-trace`: the window must hold launches only (scripts/eval_bench.py --analyze trace.csv lists it).
+synchronisations, for `rocprofv3 --hip-trace`: the window must hold launches only (scripts/eval_bench.py --analyze trace.csv lists it);
+``--protocol coco`` traces the COCO evaluator instead.
 Prints one JSON line."""
 import argparse
 import csv
@@ -44,6 +46,33 @@ def synthetic_gt(B, classes, cells, seed):
     return evaluate.device_gt(rng.randint(0, classes, first[-1]).astype(np.int32), box, (rng.uniform(size=first[-1]) < 0.1).astype(np.uint8), first)
 
 
+def coco_gt(gt, B, cells, size):
+    """The COCO fields for synthetic_gt's boxes: box area in source pixels, flags = difficult, a square image of `size` pixels."""
+    import torch
+    cls, box, dif, first = gt
+    px = float(size) / cells
+    area = (box[:, 2] - box[:, 0]) * px * ((box[:, 3] - box[:, 1]) * px)
+    return cls, box, area.contiguous(), dif, first, torch.full((B, 2), px, dtype=torch.float32, device=box.device)
+
+
+def timed_adds(ev, add, reps):
+    """(device ms per add, host microseconds inside add) after three warm-up calls; leaves ONE add in the evaluator."""
+    import torch
+    for _ in range(3):
+        add(0)
+    ev.reset()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i in range(reps):
+        add(i)
+    host_us = (time.perf_counter() - t0) / reps * 1e6          # no synchronisation inside: this is the enqueue cost
+    torch.cuda.synchronize()
+    ev.reset()
+    it = iter(range(reps))
+    ms = event_ms(lambda: add(next(it)), reps)
+    return ms, host_us
+
+
 def synthetic_records(M, C, I, N, seed):
     import numpy as np
     from yolo_tf_amd.evaluate import RECORD_DTYPE
@@ -64,9 +93,9 @@ def measure(args):
     import torch
     import bench
     import eval_ref
-    from yolo_tf_amd.evaluate import Evaluator
+    from yolo_tf_amd.evaluate import CocoEvaluator, Evaluator
     from yolo_tf_amd.session import DetectSession
-    out = {'device': torch.cuda.get_device_name(0), 'detect': {}, 'add': {}, 'result': {}}
+    out = {'device': torch.cuda.get_device_name(0), 'detect': {}, 'add': {}, 'coco_add': {}, 'result': {}}
     builder, _ = bench.make_builder('darknet', 20, 416, False, tempfile.mkdtemp())
     for B in args.batches:
         sess = DetectSession(builder, B, dtype='bf16', seed=0)
@@ -100,8 +129,21 @@ def measure(args):
             ev.reset()
             add()
             out['add']['%d/%s' % (B, mode)] = {'add_ms': ms, 'host_us_per_add': host_us, 'records': ev.result()['detections']}
+            # the COCO evaluator on the same batch, each add a batch of its own (image_base = i * B)
+            cgt = coco_gt(gt, B, 13, 416)
+            cev = CocoEvaluator(20, (args.reps + 4) * B * 100 * 20, mode=mode, threshold=thr)
+            ms, host_us = timed_adds(cev, lambda i: cev.add(sess.conf, sess.xy_min, sess.xy_max, *cgt, image_base=i * B), args.reps)
+            res = cev.result()
+            torch.cuda.synchronize()
+            t = []
+            for _ in range(args.reps):
+                t0 = time.perf_counter()
+                res = cev.result()                             # ends in its own synchronisation
+                t.append((time.perf_counter() - t0) * 1e3)
+            out['coco_add']['%d/%s' % (B, mode)] = {'add_ms': ms, 'host_us_per_add': host_us, 'records_per_add': res['detections'] // args.reps,
+                                                   'result_ms': float(np.median(t)), 'records_in_result': res['detections'], 'stats': res['stats']}
         del sess
-    for M in args.records:
+    for M in ([] if args.skip_results else args.records):
         C, I, N = 20, 4952, 845
         recs, cls, flag, npos = synthetic_records(M, C, I, N, seed=1)
         ev = Evaluator(C, M, mode='all')
@@ -129,7 +171,7 @@ def measure(args):
 def trace(args):
     import torch
     import bench
-    from yolo_tf_amd.evaluate import Evaluator
+    from yolo_tf_amd.evaluate import CocoEvaluator, Evaluator
     from yolo_tf_amd.session import DetectSession
     B = 64
     builder, _ = bench.make_builder('darknet', 20, 416, False, tempfile.mkdtemp())
@@ -137,6 +179,9 @@ def trace(args):
     sess.detect(torch.rand(B, 416, 416, 3, device='cuda') * 255.0, args.threshold, 0.45)
     gt = synthetic_gt(B, 20, 13, seed=B)
     ev = Evaluator(20, 4 * B * sess.N * 20, mode='all', threshold=args.threshold)
+    if args.protocol == 'coco':
+        gt = coco_gt(gt, B, 13, 416)
+        ev = CocoEvaluator(20, 4 * B * 100 * 20, mode='all', threshold=args.threshold)
     ev.add(sess.conf, sess.xy_min, sess.xy_max, *gt, image_base=0)
     ev.result()                                              # warm-up: allocations and code objects
     ev.reset()
@@ -147,7 +192,7 @@ def trace(args):
     res = ev.result()
     torch.cuda.synchronize()
     torch.cuda.synchronize()                                 # ... and its end
-    print(json.dumps({'detections': res['detections'], 'mAP12': res['mAP12']}))
+    print(json.dumps({'detections': res['detections'], 'mAP12': res.get('mAP12'), 'stats': res.get('stats')}))
 
 
 LAUNCH_CALLS = ('hipLaunchKernel', '__hipPushCallConfiguration', '__hipPopCallConfiguration', 'hipGetLastError')      # one kernel launch = these four
@@ -173,6 +218,8 @@ if __name__ == '__main__':
     p.add_argument('--reps', type=int, default=10)
     p.add_argument('--threshold', type=float, default=0.005)
     p.add_argument('--trace', action='store_true')
+    p.add_argument('--protocol', default='voc', choices=['voc', 'coco'], help='--trace: which evaluator runs inside the window')
+    p.add_argument('--skip_results', action='store_true', help='leave out sections 3 and 4 (the VOC sort on synthetic records and its NumPy checker)')
     p.add_argument('--analyze')
     a = p.parse_args()
     if a.analyze:

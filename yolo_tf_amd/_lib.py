@@ -104,6 +104,8 @@ SIGNATURES = {
     'yolo2_debug_set_streamk_wait_us': [_i, _i],
     'yolo2_eval_collect': [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _f, _p, _l, _p, _p, _p, _p],
     'yolo2_eval_finalize': [_p, _l, _p, _p, _i, _i, _i, _p, ctypes.c_size_t, _p, _p, _p, _p, _p],
+    'yolo2_eval_coco_collect': [_p] * 9 + [_i] * 7 + [_f, _p, _i, _p, _i, _i, _p, _l, _p, _p, _p, ctypes.c_size_t, _p],
+    'yolo2_eval_coco_finalize': [_p, _l, _p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, ctypes.c_size_t, _p, _p],
 }
 
 # host queries / diagnostics: (restype, argtypes); bound in load() next to the status-returning entries above
@@ -143,6 +145,10 @@ QUERIES = {
     'yolo2_eval_collect_workspace_bytes': (ctypes.c_size_t, [_i]),
     'yolo2_eval_workspace_bytes': (ctypes.c_size_t, [_l, _i]),
     'yolo2_eval_result_bytes': (ctypes.c_size_t, [_i]),
+    'yolo2_eval_coco_record_bytes': (ctypes.c_size_t, [_l]),
+    'yolo2_eval_coco_collect_workspace_bytes': (ctypes.c_size_t, [_i, _i, _i]),
+    'yolo2_eval_coco_workspace_bytes': (ctypes.c_size_t, [_l, _i]),
+    'yolo2_eval_coco_result_bytes': (ctypes.c_size_t, [_i, _i, _i, _i]),
 }
 
 

@@ -25,6 +25,7 @@ SOURCES = {
     'nms.hip': ['-ffp-contract=off'],
     'augment.hip': ['-ffp-contract=off'],
     'eval.hip': ['-ffp-contract=off'],
+    'eval_coco.hip': ['-ffp-contract=off'],
 }
 COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics', '-Wno-unused-result']
 LIB = os.path.join(HERE, 'libyolo2hip.so')
@@ -41,7 +42,7 @@ def _stale(out, deps):
 
 def build(force=False, verbose=True):
     hipcc = os.environ.get('HIPCC', os.path.join(ROCM, 'bin', 'hipcc'))
-    headers = [os.path.join(HERE, 'common.h'), os.path.join(HERE, 'conv_shared.h'), os.path.join(HERE, '..', '..', 'include', 'yolo2_hip.h'), os.path.abspath(__file__)]
+    headers = [os.path.join(HERE, 'common.h'), os.path.join(HERE, 'conv_shared.h'), os.path.join(HERE, 'eval_sort.h'), os.path.join(HERE, '..', '..', 'include', 'yolo2_hip.h'), os.path.abspath(__file__)]
     objs, cmds = [], []
     for src, extra in SOURCES.items():
         s = os.path.join(HERE, src)

@@ -15,7 +15,7 @@
 //                      minimum, FP (duplicate) when it is not, ignored when the candidate is difficult, FP when nothing overlaps enough.
 //   eval_bump_kernel   adds the batch's count to the device word.
 // Stage B (yolo2_eval_finalize, once per evaluation):
-//   LSD radix sort of the 16-byte records, 8 bits per pass (histogram per 16384-record tile, one-workgroup scan of the digit x tile
+//   LSD radix sort of the 16-byte records (eval_sort.h, shared with eval_coco.hip), 8 bits per pass (histogram per 16384-record tile, one-workgroup scan of the digit x tile
 //   table, stable scatter), over box index, image index, inverted score bits and class key: the result is ordered by (class, score
 //   desc, image asc, box asc) whatever the order of the collect calls.  Ignored records carry class key C + class and sort behind.
 //   eval_ap_kernel, one workgroup per class: binary search of the class segment, integer scans of TP / FP over per-thread contiguous
@@ -23,59 +23,10 @@
 //   maximum of the precision.  Every f64 sum has a fixed association, so two runs give the same bits.
 // IoU is f32 in the reference's operation order ((a1+a2)-inter, floor 1e-10; utils/postprocess.py:21-36) with FP contraction off, as
 // in nms.hip.
-#include "common.h"
+#include "eval_sort.h"
 #pragma clang fp contract(off)
 
-#define EV_TILE_ITEMS 64
-#define EV_TILE (256 * EV_TILE_ITEMS)       // records per workgroup of a radix pass
 #define EV_AP_THREADS 1024
-#define EV_ERR_GT_CLASS 1ull                 // a ground truth class id outside [0, C)
-#define EV_ERR_GT_FIRST 2ull                 // gt_first not ascending inside [0, G], or more than YOLO2_EVAL_MAX_GT_PER_IMAGE boxes in an image
-#define EV_ERR_RECORD 4ull                   // a record's image / box index outside what finalize was told
-
-__device__ __forceinline__ unsigned ev_ord(float s) {        // ascending in this <=> ascending score
-    const unsigned b = __builtin_bit_cast(unsigned, s);
-    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float ev_iou(const f32x4 p, const f32x4 q) {
-    const float a1 = (p[2] - p[0]) * (p[3] - p[1]);
-    const float a2 = (q[2] - q[0]) * (q[3] - q[1]);
-    const float w = fmaxf(fminf(p[2], q[2]) - fmaxf(p[0], q[0]), 0.0f);
-    const float h = fmaxf(fminf(p[3], q[3]) - fmaxf(p[1], q[1]), 0.0f);
-    const float inter = w * h;
-    return inter / fmaxf((a1 + a2) - inter, 1e-10f);
-}
-// item `it` of image row `conf` -> is it a detection, and which (box, class, score)
-__device__ __forceinline__ bool ev_item(const float *__restrict__ conf, int it, int items, int C, float thr, int mode, int &box, int &cls, float &score) {
-    if (it >= items) return false;
-    if (mode == YOLO2_EVAL_MODE_ALL) {
-        box = it / C;
-        cls = it - box * C;
-        score = conf[it] + 0.0f;                         // (-0 -> +0: one bit pattern per value, the order key is the bits)
-        return score > thr;
-    }
-    box = it;
-    const float *row = conf + (long)it * C;
-    float best = row[0];
-    bool nan = best != best;
-    int arg = 0;
-    for (int c = 1; c < C; ++c) {
-        const float v = row[c];
-        nan |= v != v;
-        if (v > best) { best = v; arg = c; }           // strict: the FIRST arg-max
-    }
-    cls = arg;
-    score = best + 0.0f;
-    return !nan && score > thr;
-}
-__device__ __forceinline__ int ev_block_sum(int v, int *sred) {      // 256 threads; every thread gets the sum
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return sred[0] + sred[1] + sred[2] + sred[3];
-}
 
 __global__ __launch_bounds__(256) void eval_count_kernel(const float *__restrict__ conf, int *__restrict__ counts, int N, int C, float thr, int mode) {
     __shared__ int sred[4];
@@ -208,106 +159,19 @@ __device__ __forceinline__ unsigned ev_class_key(unsigned cf, int C) {
     const unsigned cls = cf >> 2;
     return (cf & 3u) == YOLO2_EVAL_IGNORED ? (unsigned)C + cls : cls;
 }
-__device__ __forceinline__ unsigned ev_field(const u32x4 r, int field, int C) {
-    switch (field) {
-    case 0: return r[2];
-    case 1: return r[1];
-    case 2: return ~ev_ord(__builtin_bit_cast(float, r[0]));      // descending score
-    default: return ev_class_key(r[3], C);
-    }
-}
-__device__ __forceinline__ long ev_count(const unsigned long long *state, long capacity) {
-    const unsigned long long n = state[0];
-    return n < (unsigned long long)capacity ? (long)n : capacity;
-}
-
-__global__ __launch_bounds__(256) void eval_hist_kernel(const u32x4 *__restrict__ src, unsigned long long *__restrict__ state, long capacity,
-                                                        int *__restrict__ table, int field, int shift, int C, int check, int n_images, int N) {
-    __shared__ int h[256];
-    const long M = ev_count(state, capacity);
-    const long lo = (long)blockIdx.x * EV_TILE, hi = min(lo + EV_TILE, M);
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    bool bad = false;
-    for (long i = lo + threadIdx.x; i < hi; i += 256) {
-        const u32x4 r = src[i];
-        atomicAdd(&h[(ev_field(r, field, C) >> shift) & 255u], 1);
-        if (check) bad |= r[1] >= (unsigned)n_images || r[2] >= (unsigned)N || (r[3] >> 2) >= (unsigned)C;
-    }
-    if (bad) atomicOr(&state[1], EV_ERR_RECORD);
-    __syncthreads();
-    table[(long)blockIdx.x * 256 + threadIdx.x] = h[threadIdx.x];
-}
-
-// table[tile][digit] counts -> start positions, ordered digit-major, tile-minor
-__global__ __launch_bounds__(256) void eval_scan_kernel(int *__restrict__ table, int tiles) {
-    __shared__ int tot[256];
-    const int d = threadIdx.x;
-    int s = 0;
-    for (int j = 0; j < tiles; ++j) s += table[(long)j * 256 + d];
-    tot[d] = s;
-    __syncthreads();
-    int off = 0;
-    for (int k = 0; k < d; ++k) off += tot[k];
-    for (int j = 0; j < tiles; ++j) {
-        const int v = table[(long)j * 256 + d];
-        table[(long)j * 256 + d] = off;
-        off += v;
-    }
-}
-
-__global__ __launch_bounds__(256) void eval_scatter_kernel(const u32x4 *__restrict__ src, u32x4 *__restrict__ dst, const unsigned long long *__restrict__ state,
-                                                           long capacity, const int *__restrict__ table, int field, int shift, int C) {
-    __shared__ int base[256];
-    __shared__ int wcnt[4][256];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long M = ev_count(state, capacity);
-    const long lo = (long)blockIdx.x * EV_TILE;
-    if (lo >= M) return;                                    // (uniform for the workgroup)
-    const long hi = min(lo + EV_TILE, M);
-    base[tid] = table[(long)blockIdx.x * 256 + tid];
-#pragma unroll
-    for (int w = 0; w < 4; ++w) wcnt[w][tid] = 0;
-    __syncthreads();
-    for (long c0 = lo; c0 < hi; c0 += 256) {
-        const long i = c0 + tid;
-        const bool valid = i < hi;
-        u32x4 r = {0u, 0u, 0u, 0u};
-        unsigned d = 0;
-        if (valid) {
-            r = src[i];
-            d = (ev_field(r, field, C) >> shift) & 255u;
+struct ev_voc_field {                    // the sort fields of a yolo2_eval_record (eval_sort.h)
+    static __device__ __forceinline__ unsigned get(const u32x4 r, int field, int C) {
+        switch (field) {
+        case 0: return r[2];
+        case 1: return r[1];
+        case 2: return ~ev_ord(__builtin_bit_cast(float, r[0]));      // descending score
+        default: return ev_class_key(r[3], C);
         }
-        // the lanes of this wave with the same digit: eight ballots
-        unsigned long long peers = __ballot(valid);
-#pragma unroll
-        for (int bit = 0; bit < 8; ++bit) {
-            const bool one = (d >> bit) & 1u;
-            const unsigned long long m = __ballot(valid && one);
-            peers &= one ? m : ~m;
-        }
-        const int rank = __popcll(peers & ((1ull << lane) - 1ull));
-        if (valid && rank == 0) wcnt[wave][d] = __popcll(peers);
-        __syncthreads();
-        if (valid) {
-            int pos = base[d] + rank;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) pos += w < wave ? wcnt[w][d] : 0;
-            if (pos >= 0 && (long)pos < M) dst[pos] = r;       // (always true when the table belongs to these records)
-        }
-        __syncthreads();
-        {
-            int add = 0;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                add += wcnt[w][tid];
-                wcnt[w][tid] = 0;
-            }
-            base[tid] += add;
-        }
-        __syncthreads();
     }
-}
+    static __device__ __forceinline__ bool bad(const u32x4 r, int n_images, int N, int C) {
+        return r[1] >= (unsigned)n_images || r[2] >= (unsigned)N || (r[3] >> 2) >= (unsigned)C;
+    }
+};
 
 __device__ __forceinline__ long ev_lower_bound(const u32x4 *__restrict__ recs, long M, unsigned key, int C) {
     long a = 0, b = M;
@@ -423,13 +287,6 @@ __global__ __launch_bounds__(EV_AP_THREADS) void eval_ap_kernel(const u32x4 *__r
     }
 }
 
-static int ev_bytes_for(unsigned long long max_value) {       // 8-bit digits needed for values 0 .. max_value
-    int n = 1;
-    while (n < 4 && (max_value >> (8 * n))) ++n;
-    return n;
-}
-static long ev_tiles(long max_records) { return (max_records + EV_TILE - 1) / EV_TILE; }
-static size_t ev_align(size_t v) { return (v + 255) / 256 * 256; }
 
 extern "C" size_t yolo2_eval_record_bytes(long max_records) { return max_records > 0 ? (size_t)max_records * sizeof(yolo2_eval_record) : 0; }
 extern "C" size_t yolo2_eval_collect_workspace_bytes(int B) { return B > 0 ? (size_t)B * sizeof(int) : 0; }
@@ -479,11 +336,11 @@ extern "C" int yolo2_eval_finalize(const void *records, long max_records, unsign
     int which = 0, first = 1;
     for (int k = 0; k < 4; ++k)
         for (int byte = 0; byte < keys[k].bytes; ++byte) {
-            eval_hist_kernel<<<tiles, 256, 0, st>>>(src, state, max_records, table, keys[k].field, 8 * byte, C, first, n_images, N);
+            eval_hist_kernel<ev_voc_field><<<tiles, 256, 0, st>>>(src, state, max_records, table, keys[k].field, 8 * byte, C, first, n_images, N);
             Y2_CHECK_LAUNCH();
             eval_scan_kernel<<<1, 256, 0, st>>>(table, tiles);
             Y2_CHECK_LAUNCH();
-            eval_scatter_kernel<<<tiles, 256, 0, st>>>(src, buf[which], state, max_records, table, keys[k].field, 8 * byte, C);
+            eval_scatter_kernel<ev_voc_field><<<tiles, 256, 0, st>>>(src, buf[which], state, max_records, table, keys[k].field, 8 * byte, C);
             Y2_CHECK_LAUNCH();
             src = buf[which];
             which ^= 1;

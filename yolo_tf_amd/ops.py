@@ -2,6 +2,7 @@
 stream plumbing here).  Used by the engine and by the per-kernel parity tests."""
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -574,3 +575,32 @@ def eval_finalize(records, max_records, state, npos, C, n_images, N, ws, results
     """Stage B of the evaluator (yolo2_eval_finalize): device sort per class + both VOC average precisions into ``results``; asynchronous."""
     call('yolo2_eval_finalize', ptr(records), max_records, ptr(state), ptr(npos), C, n_images, N, ptr(ws), ws.numel() * ws.element_size(),
          ptr(results), ptr(sorted_records), ptr(cum_tp), ptr(cum_fp), _stream())
+
+
+# COCO protocol (include/yolo2_hip.h, section "evaluation, COCO protocol")
+def _host(a, dtype):
+    """A host table as (pointer or None, the array that keeps it alive): the library reads it during the call."""
+    if a is None:
+        return None, None
+    a = np.ascontiguousarray(a, dtype)
+    return a.ctypes.data, a
+
+
+def eval_coco_collect(conf, xy_min, xy_max, gt_class, gt_box, gt_area, gt_flags, gt_first, scale, G, B, N, C, n_valid, image_base, mode, threshold,
+                      area_ranges, A, iou_thresholds, T, max_dets, records, max_records, state, npig, ws):
+    """Stage A of the COCO evaluator (yolo2_eval_coco_collect): greedy matching per (area range, IoU threshold) and the records of
+    this batch; asynchronous.  area_ranges [A,2] f32 and iou_thresholds [T] f32 are HOST arrays."""
+    pa, _ka = _host(area_ranges, np.float32)
+    pt, _kt = _host(iou_thresholds, np.float32)
+    call('yolo2_eval_coco_collect', ptr(conf), ptr(xy_min), ptr(xy_max), ptr(gt_class), ptr(gt_box), ptr(gt_area), ptr(gt_flags), ptr(gt_first),
+         ptr(scale), G, B, N, C, n_valid, image_base, mode, threshold, pa, A, pt, T, max_dets, ptr(records), max_records, ptr(state), ptr(npig),
+         ptr(ws), 0 if ws is None else ws.numel() * ws.element_size(), _stream())
+
+
+def eval_coco_finalize(records, max_records, state, npig, C, n_images, N, A, T, max_dets, slices, S, recall_thresholds, R, ws, results):
+    """Stage B of the COCO evaluator (yolo2_eval_coco_finalize): device sort + AP / recall per (slice, threshold, class) into
+    ``results``; asynchronous.  slices [S,2] int32 and recall_thresholds [R] f64 are HOST arrays."""
+    ps, _ks = _host(slices, np.int32)
+    pr, _kr = _host(recall_thresholds, np.float64)
+    call('yolo2_eval_coco_finalize', ptr(records), max_records, ptr(state), ptr(npig), C, n_images, N, A, T, max_dets, ps, S, pr, R, ptr(ws),
+         0 if ws is None else ws.numel() * ws.element_size(), ptr(results), _stream())
