@@ -117,7 +117,8 @@ def test_train_step_matches_oracle(basedir, inference, size, dtype, B):
         # correlation) is comparable to the residue mu_x * sum(rounding errors of dy), and two valid bf16 computations
         # (this engine, the bf16-storage oracle) diverge chaotically layer by layer (scripts/debug_bwd.py shows 1-ulp
         # agreement in the first layers growing ~1.3x per layer).  Equality is pinned per kernel (test_kernels_gpu.py,
-        # bf16 cases) and for the whole network in f32 (above); here: same loss, same gradient scale, same direction.
+        # bf16 cases; the loss and decode kernels in test_head_gpu.py, bf16 cases) and for the whole network in f32 (above);
+        # here: same loss, same gradient scale, same direction.
         ratio = sorted((np.linalg.norm(grads[k].astype(np.float64)) / (np.linalg.norm(info['grads'][k].astype(np.float64)) + 1e-300), k) for k in grads)
         med = float(np.median([c for c, _ in cs]))
         print('bf16: median gradient cosine %.3f, min %.3f (%s); gradient norm ratio in [%.2f, %.2f]' % (med, cs[0][0], cs[0][1], ratio[0][0], ratio[-1][0]))
