@@ -676,6 +676,37 @@ int yolo2_eval_coco_finalize(const void *records, long max_records, unsigned lon
                              int A, int T, int max_dets, const int *slices, int S, const double *recall_thresholds, int R, void *ws,
                              size_t ws_bytes, void *results, void *stream);
 
+/* ---- dimension clusters: the anchors of a dataset (new work).  The reference lists "Dimension cluster" as an unchecked roadmap item
+ * (README.md:88) and has no code for it; every YOLOv2 model reads the result through `[yolo2] anchors` (model/yolo2/__init__.py:106).
+ * The method is YOLO9000 (Redmon & Farhadi 2016), section 2 "Dimension Clusters": k-means over the ground truth boxes' (w, h) with
+ * distance 1 - IoU.  Many JOBS = (k, centroids) run in one launch; one Lloyd iteration is yolo2_anchor_assign + yolo2_anchor_update.
+ *
+ * boxes [n][2] f32 = (w, h) in grid-cell units (the unit of config/yolo2/anchors/ *.tsv), 16-byte aligned, 1 <= n <=
+ * YOLO2_ANCHOR_MAX_BOXES, every value finite with 2^-12 <= v < 2^12 (the caller checks the values: the fixed-point sums below rely on it).
+ * centroids [jobs][kmax][2] f32, job_k [jobs] int with 1 <= job_k <= kmax <= YOLO2_ANCHOR_MAX_K; slots at and past job_k are never
+ * read or written.  jobs <= YOLO2_ANCHOR_MAX_JOBS.
+ * Assign: for box (w, h) and centroid (cw, ch), f32, no contraction, in this order: inter = min(w,cw) * min(h,ch); uni = (w*h + cw*ch)
+ *   - inter; iou = inter / uni (correctly rounded).  The box belongs to the centroid of largest iou, of equal ones to the lowest index.
+ *   Into ws, per job: per cluster count, sum of rint(w * 2^24), sum of rint(h * 2^24) (rint of the f64 product, half to even), then one
+ *   sum of rint(best_iou * 2^30): 64-bit integers, so the sums are exact and the same whatever the order of the adds.
+ *   done [jobs] (may be NULL): a job with done != 0 is skipped.  assignment (may be NULL): [jobs][n] bytes, the cluster of every box.
+ * Update (done and iterations given): a non-empty cluster's centroid becomes (float)((double)sum / (double)count * 2^-24) for w and h;
+ *   an empty one keeps its bits.  iterations[job] += 1; when no centroid of the job changed bitwise, done[job] = 1 (with exact sums:
+ *   no box changed cluster).  A job with done != 0 on entry is left alone altogether.
+ * Score (done and iterations both NULL): the centroids stay; counts and / or avg_iou are required.
+ * Both passes: counts [jobs][kmax] int64 and avg_iou [jobs] f64 = sum / 2^30 / n (each may be NULL) describe the assignment just
+ *   consumed, i.e. the centroids yolo2_anchor_assign ran with, and the job's workspace words are cleared.
+ * ws: yolo2_anchor_workspace_bytes(jobs, kmax) = 8 * jobs * (3 * kmax + 1) bytes, zeroed by the caller ONCE, at allocation.
+ * n of the update call is the n of the assign call it follows. */
+#define YOLO2_ANCHOR_MAX_K 32
+#define YOLO2_ANCHOR_MAX_JOBS 65535
+#define YOLO2_ANCHOR_MAX_BOXES ((1 << 27) - 1)
+size_t yolo2_anchor_workspace_bytes(int jobs, int kmax);           /* 0 for arguments out of range */
+int yolo2_anchor_assign(const float *boxes, int n, const float *centroids, const int *job_k, int jobs, int kmax,
+                        unsigned long long *ws, size_t ws_bytes, const int *done, unsigned char *assignment, void *stream);
+int yolo2_anchor_update(float *centroids, const int *job_k, int jobs, int kmax, unsigned long long *ws, size_t ws_bytes, int n,
+                        int *done, int *iterations, long long *counts, double *avg_iou, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

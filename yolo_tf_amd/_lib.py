@@ -106,6 +106,8 @@ SIGNATURES = {
     'yolo2_eval_finalize': [_p, _l, _p, _p, _i, _i, _i, _p, ctypes.c_size_t, _p, _p, _p, _p, _p],
     'yolo2_eval_coco_collect': [_p] * 9 + [_i] * 7 + [_f, _p, _i, _p, _i, _i, _p, _l, _p, _p, _p, ctypes.c_size_t, _p],
     'yolo2_eval_coco_finalize': [_p, _l, _p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, ctypes.c_size_t, _p, _p],
+    'yolo2_anchor_assign': [_p, _i, _p, _p, _i, _i, _p, ctypes.c_size_t, _p, _p, _p],
+    'yolo2_anchor_update': [_p, _p, _i, _i, _p, ctypes.c_size_t, _i, _p, _p, _p, _p, _p],
 }
 
 # host queries / diagnostics: (restype, argtypes); bound in load() next to the status-returning entries above
@@ -149,6 +151,7 @@ QUERIES = {
     'yolo2_eval_coco_collect_workspace_bytes': (ctypes.c_size_t, [_i, _i, _i]),
     'yolo2_eval_coco_workspace_bytes': (ctypes.c_size_t, [_l, _i]),
     'yolo2_eval_coco_result_bytes': (ctypes.c_size_t, [_i, _i, _i, _i]),
+    'yolo2_anchor_workspace_bytes': (ctypes.c_size_t, [_i, _i]),
 }
 
 

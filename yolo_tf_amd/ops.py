@@ -604,3 +604,22 @@ def eval_coco_finalize(records, max_records, state, npig, C, n_images, N, A, T, 
     pr, _kr = _host(recall_thresholds, np.float64)
     call('yolo2_eval_coco_finalize', ptr(records), max_records, ptr(state), ptr(npig), C, n_images, N, A, T, max_dets, ps, S, pr, R, ptr(ws),
          0 if ws is None else ws.numel() * ws.element_size(), ptr(results), _stream())
+
+
+# dimension clusters (include/yolo2_hip.h, section "dimension clusters")
+ANCHOR_MAX_K = 32                          # YOLO2_ANCHOR_MAX_K
+ANCHOR_MAX_JOBS = 65535                    # YOLO2_ANCHOR_MAX_JOBS
+ANCHOR_MAX_BOXES = (1 << 27) - 1           # YOLO2_ANCHOR_MAX_BOXES
+
+
+def anchor_assign(boxes, n, centroids, job_k, jobs, kmax, ws, done=None, assignment=None):
+    """yolo2_anchor_assign: every box's best centroid (IoU of (w, h)) of every job, summed into the integer workspace; asynchronous."""
+    call('yolo2_anchor_assign', ptr(boxes), n, ptr(centroids), ptr(job_k), jobs, kmax, ptr(ws), 0 if ws is None else ws.numel() * ws.element_size(),
+         ptr(done), ptr(assignment), _stream())
+
+
+def anchor_update(centroids, job_k, jobs, kmax, ws, n, done=None, iterations=None, counts=None, avg_iou=None):
+    """yolo2_anchor_update: with ``done`` and ``iterations`` the Lloyd update (new centroids, fixed point detection); without both the
+    score pass (centroids stay).  Either writes ``counts`` / ``avg_iou`` when given and clears the workspace; asynchronous."""
+    call('yolo2_anchor_update', ptr(centroids), ptr(job_k), jobs, kmax, ptr(ws), 0 if ws is None else ws.numel() * ws.element_size(), n,
+         ptr(done), ptr(iterations), ptr(counts), ptr(avg_iou), _stream())
