@@ -82,6 +82,16 @@ def assert_wgrad_exact_products(got, ref, what):
         what, int((ratio > 1).sum()), ratio.size, WGRAD_REL, WGRAD_FLOOR, scale, worst)
 
 
+def part_row_sums(ops, part, C):
+    """The row contract of a statistics-producing launch, read BEFORE a consumer clears the rows: the kernel wrote only the rows the host
+    counted (yolo2_last_bn_part_rows; the folded consumers sum exactly those).  -> (R, f64 sums of plane 0 and of plane 1 over rows [0, R))."""
+    rows = ops.last_bn_part_rows()
+    p = host(part).astype(np.float64).reshape(2, 256, C)
+    assert 1 <= rows <= 256, rows
+    assert (p[:, rows:] == 0).all(), ('rows beyond last_bn_part_rows() were written', rows, np.nonzero(p[:, rows:].any(axis=(0, 2)))[0][:8] + rows)
+    return rows, p[0, :rows].sum(0), p[1, :rows].sum(0)
+
+
 def pad_channels(x, ld):
     out = np.zeros(x.shape[:-1] + (ld,), x.dtype)
     out[..., :x.shape[-1]] = x
@@ -197,7 +207,8 @@ def test_conv_forward_ksliced(ops, shape, mode):
                                    (2, 13, 13, 512, 256, 3),     # K-sliced grid -> fallback
                                    (8, 13, 13, 1024, 504, 3),    # stream-K: owners hold the finished tiles
                                    (3, 20, 20, 32, 64, 3),       # 64-filter tile
-                                   (2, 13, 13, 128, 256, 1)])
+                                   (2, 13, 13, 128, 256, 1),
+                                   (1, 65, 64, 72, 136, 3)])     # generic kernel, 33 pixel tiles (the last half full) x 4 wave rows: the rows wrap; ragged channels and filter tile
 def test_conv_bn_fused_statistics(ops, shape, mode):
     """yolo2_conv2d_bn + yolo2_bn_finalize: same output as yolo2_conv2d_ws, batch moments of the STORED output (tf.nn.moments
     semantics, biased variance), moving averages updated with decay 0.999, partial buffer left zero."""
@@ -221,6 +232,10 @@ def test_conv_bn_fused_statistics(ops, shape, mode):
     mm, mv = dev(mm0), dev(mv0)
     mean, var = torch.zeros(Cout, device='cuda'), torch.zeros(Cout, device='cuda')
     ops.conv2d_bn(xd, F, y, ws, B, H, W, ldx, ldx, Cout, Cout, k, mm, part)
+    rows, s1, s2 = part_row_sums(ops, part, Cout)        # (before bn_finalize clears the rows; shifted sums: shift = mm0)
+    if shape == (1, 65, 64, 72, 136, 3):
+        # 132 (pixel tile, wave row) pairs: bf16 consumers read at most 128 rows of 136 channels -> wrapped around 16 with atomic adds; f32: 256 -> one row each
+        assert rows == (132 if mode == 'f32' else 16), (rows, ops.last_conv_plan())
     ops.bn_finalize(part, mm, M, Cout, mean, var, mm, mv, 0.999)
     torch.cuda.synchronize()
     # (K-sliced grids accumulate with f32 atomics: the summation order, hence the last bit, varies between launches)
@@ -231,6 +246,9 @@ def test_conv_bn_fused_statistics(ops, shape, mode):
     scale = np.sqrt(v_ref).max()
     assert np.abs(host(mean) - m_ref).max() <= 2e-5 * scale + 1e-6
     assert np.abs(host(var) - v_ref).max() <= 1e-4 * v_ref.max()
+    # ... and the rows the host counted hold those moments on their own
+    assert np.abs(mm0 + s1 / M - m_ref).max() <= 2e-5 * scale + 1e-6, rows
+    assert np.abs(s2 / M - (s1 / M) ** 2 - v_ref).max() <= 1e-4 * v_ref.max(), rows
     np.testing.assert_allclose(host(mm), mm0 - (mm0 - host(mean)) * np.float32(1 - 0.999), rtol=1e-6, atol=1e-7)
     np.testing.assert_allclose(host(mv), mv0 - (mv0 - host(var)) * np.float32(1 - 0.999), rtol=1e-6, atol=1e-7)
 
@@ -395,6 +413,8 @@ def test_conv_tap_fused_3x3(ops, shape, variant, epilogue):
     ws = torch.full((1024 + 256 * 256 * 128,), 3.0, dtype=torch.float32, device='cuda')
     bias = dev(rng.randn(Cout).astype(np.float32))
     out = {}
+    check_rows = shape in _tiny or shape == (9, 52, 52, 128, 256)      # (the row contract, on the shapes whose device-to-host copy is small)
+    row_sums = {}
     for tap in (0, 1):
         ops.set_igemm_tap(mode if tap else 0)
         ops.set_pp(grid=pp_grid, dmapos=pp_dma, min_steps=0, min_share=0)      # every shape of this test takes the ping-pong kernel (dmapos < 0: keep the default SCHED)
@@ -411,6 +431,8 @@ def test_conv_tap_fused_3x3(ops, shape, variant, epilogue):
                 shift = dev(rng.randn(Cout).astype(np.float32) * 0.05) if tap == 0 else out[0][2][3]
                 mean, var = torch.zeros(Cout, device='cuda'), torch.zeros(Cout, device='cuda')
                 ops.conv2d_bn(xd, F, O, ws, B, H, W, Cin, Cin, Cout, Cout, k, shift, part)
+                if check_rows:
+                    row_sums[tap] = part_row_sums(ops, part, Cout)
                 ops.bn_finalize(part, shift, M, Cout, mean, var, None, None, 0.999)
                 extra = (mean, var, part, shift)
             else:
@@ -425,6 +447,8 @@ def test_conv_tap_fused_3x3(ops, shape, variant, epilogue):
                 red = torch.zeros(ops.workspace_bytes('bn', Cout) // 8, dtype=torch.float64, device='cuda')
                 dg, db = torch.zeros(Cout, device='cuda'), torch.zeros(Cout, device='cuda')
                 if ops.conv2d_dgrad_bn(xd, F, O, ws, B, H, W, Cin, Cin, Cout, ldo, k, yprev, pm, pv, pg, pb, dg, db, part, red, 1e-3, 0.1):
+                    if check_rows:
+                        row_sums[tap] = part_row_sums(ops, part, Cout)
                     ops.bn_part_to_grads(part, Cout, dg, db)
                 extra = (dg, db, part, None, yprev, pm, pv, pg, pb)
             plan = ops.last_conv_plan()
@@ -457,6 +481,10 @@ def test_conv_tap_fused_3x3(ops, shape, variant, epilogue):
         yh = y1.astype(np.float64)
         assert np.abs(host(out[1][2][0]) - yh.mean(0)).max() <= 2e-5 * np.sqrt(yh.var(0)).max() + 1e-6
         assert np.abs(host(out[1][2][1]) - yh.var(0)).max() <= 1e-4 * yh.var(0).max()
+        for tap, (rows, s1, s2) in row_sums.items():      # the rows the host counted hold the moments of that launch's stored output
+            yt, sh = out[tap][0].astype(np.float64), host(out[0][2][3]).astype(np.float64)
+            assert np.abs(sh + s1 / M - yt.mean(0)).max() <= 2e-5 * np.sqrt(yt.var(0)).max() + 1e-6, (tap, rows)
+            assert np.abs(s2 / M - (s1 / M) ** 2 - yt.var(0)).max() <= 1e-4 * yt.var(0).max(), (tap, rows)
     if epilogue == 'dgrad_bn':
         for a, b, name in ((out[1][2][0], out[0][2][0], 'dgamma'), (out[1][2][1], out[0][2][1], 'dbeta')):
             assert np.abs(host(a) - host(b)).max() <= 2e-2 * np.abs(host(b)).max(), name
@@ -467,6 +495,10 @@ def test_conv_tap_fused_3x3(ops, shape, variant, epilogue):
         dg_o, db_o = _bn_bwd_sums_oracle(y1[:, :Cout], host(yprev).reshape(M, Cout), host(pm), host(pv), host(pg), host(pb), 1e-3)
         for got, ref, name in ((out[1][2][0], dg_o, 'dgamma'), (out[1][2][1], db_o, 'dbeta')):
             assert np.abs(host(got) - ref).max() <= 3e-3 * np.abs(ref).max(), (name, np.abs(host(got) - ref).max(), np.abs(ref).max())
+        for tap, (rows, s1, s2) in row_sums.items():      # the rows the host counted hold the sums of that launch's stored gradient
+            dg_t, db_t = (dg_o, db_o) if tap else _bn_bwd_sums_oracle(y0[:, :Cout], host(yprev).reshape(M, Cout), host(pm), host(pv), host(pg), host(pb), 1e-3)
+            for got, ref, name in ((s1, dg_t, 'dgamma rows'), (s2, db_t, 'dbeta rows')):
+                assert np.abs(got - ref).max() <= 3e-3 * np.abs(ref).max(), (name, tap, rows, np.abs(got - ref).max(), np.abs(ref).max())
 
 
 def test_streamk_unserviceable_grid_surfaces_as_error(ops):
@@ -551,6 +583,7 @@ def test_conv_dgrad_bn_fused_sums(ops, shape, fused, mode):
     if mode == 'bf16':                     # (f32 tiles of some variants do not fit the LDS image: those run the two-step form)
         assert pending == (fused and os.environ.get('YOLO2_FUSE_BN_BWD', '1') != '0'), (pending, plan)
     if pending:
+        rows, s1, s2 = part_row_sums(ops, part, Cin)        # (before bn_part_to_grads clears the rows)
         ops.bn_part_to_grads(part, Cin, dg, db)
     torch.cuda.synchronize()
     # (stream-K / K-sliced grids add partial tiles in a launch-dependent order: last-bit differences in dX between launches)
@@ -573,6 +606,9 @@ def test_conv_dgrad_bn_fused_sums(ops, shape, fused, mode):
     dg_o, db_o = _bn_bwd_sums_oracle(dx_g, host(yprev).reshape(M, Cin), host(mean), host(var), host(gamma), host(beta), 1e-3)
     for got, ref, name in ((dg, dg_o, 'dgamma'), (db, db_o, 'dbeta')):
         assert np.abs(host(got) - ref).max() <= (3e-4 if mode == 'f32' else 3e-3) * np.abs(ref).max(), (name, shape, mode)
+    if pending:      # ... and the rows the host counted hold those sums on their own
+        for got, ref, name in ((s1, dg_o, 'dgamma rows'), (s2, db_o, 'dbeta rows')):
+            assert np.abs(got - ref).max() <= (3e-4 if mode == 'f32' else 3e-3) * np.abs(ref).max(), (name, rows, shape, mode)
 
 
 WGRAD_SHAPES = CONV_SHAPES + [(2, 13, 13, 256, 128, 3), (2, 26, 26, 128, 256, 1), (4, 52, 52, 32, 64, 3)]

@@ -43,7 +43,8 @@ def _stale(out, deps):
 
 def build(force=False, verbose=True):
     hipcc = os.environ.get('HIPCC', os.path.join(ROCM, 'bin', 'hipcc'))
-    headers = [os.path.join(HERE, 'common.h'), os.path.join(HERE, 'conv_shared.h'), os.path.join(HERE, 'eval_sort.h'), os.path.join(HERE, '..', '..', 'include', 'yolo2_hip.h'), os.path.abspath(__file__)]
+    # every header of this directory: editing any of them rebuilds
+    headers = sorted(os.path.join(HERE, h) for h in os.listdir(HERE) if h.endswith('.h')) + [os.path.join(HERE, '..', '..', 'include', 'yolo2_hip.h'), os.path.abspath(__file__)]
     objs, cmds = [], []
     for src, extra in SOURCES.items():
         s = os.path.join(HERE, src)

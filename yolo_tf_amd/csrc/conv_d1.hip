@@ -13,11 +13,11 @@
 // Same arithmetic and rounding points as the generic epilogue (conv_igemm.hip): dX rounded to bf16, dz = dX_rounded * leaky'(z), xhat from the stored y.
 #include "common.h"
 #include "conv_shared.h"
+#include "conv_epilogue.h"
 #include <atomic>
 
 #define D1_BM 128
 #define D1_BN 128
-#define D1_STAT_ROWS 32
 
 // KCH = 16-channel groups of the reduction (4: 64 input channels of the data gradient, 8: 128).  ABL (experiments): +1 no output stores, +2 no y loads,
 // +4 no sums arithmetic
@@ -62,20 +62,8 @@ __global__ __launch_bounds__(512) void conv_d1_dgrad_bn_kernel(
 
     // ---- per-lane constants of the store loop: this lane's eight channels nb .. nb + 7 (the same in every iteration of every tile)
     const int nb = n0 + wn * 64 + (lane % WCPR) * VEC;
-    float cmu[VEC], cinv[VEC], cga[VEC], cbt[VEC], ps[2][VEC];
-#pragma unroll
-    for (int k = 0; k < VEC; k += 4) {
-        const f32x4 a = *reinterpret_cast<const f32x4 *>(bz.mean + nb + k), b = *reinterpret_cast<const f32x4 *>(bz.var + nb + k);
-        const f32x4 c = *reinterpret_cast<const f32x4 *>(bz.gamma + nb + k), d = *reinterpret_cast<const f32x4 *>(bz.beta + nb + k);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            cmu[k + q] = a[q];
-            cinv[k + q] = 1.0f / sqrtf(b[q] + bz.eps);
-            cga[k + q] = c[q];
-            cbt[k + q] = d[q];
-            ps[0][k + q] = ps[1][k + q] = 0.f;
-        }
-    }
+    Y2BnBwdLane<T> bw;
+    bw.load(bz, nb);
     // y vectors of the lane's NIT store positions of a tile: (row, chunk) = ((it * 64 + lane) / 8, lane % 8) of wave row wm
     Vec16<T> ycur[NIT], ynext[NIT];
     auto load_y = [&](int tile_) {
@@ -140,49 +128,20 @@ __global__ __launch_bounds__(512) void conv_d1_dgrad_bn_kernel(
             const f32x4 v = *reinterpret_cast<const f32x4 *>(wreg + row * WSTRIDE + ch * 16);
             if (m < M) {
                 if (!(ABL & 1)) *reinterpret_cast<f32x4 *>(O + (long)m * Nf + nb) = v;
-                const Vec16<T> y = ycur[it];
-                Vec16<T> d;
-                d.v = __builtin_bit_cast(decltype(d.v), v);
-                if (ABL & 4) { ps[0][it] += d.get(0) + y.get(1); continue; }
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) {
-                    const float xh = (y.get(k) - cmu[k]) * cinv[k];
-                    const float z = (y.get(k) - cmu[k]) * (cinv[k] * cga[k]) + cbt[k];
-                    const float g = z >= 0.f ? d.get(k) : bz.alpha * d.get(k);
-                    ps[0][k] += g * xh;
-                    ps[1][k] += g;
-                }
+                const Vec16<T> y = ycur[it], d = y2_as_vec16<T>(v);
+                if (ABL & 4) { bw.ps[0][it] += d.get(0) + y.get(1); continue; }
+                bw.add(bz, y, d);
             }
         }
     }
-    // ---- the lanes that share a channel chunk meet (lane % 8 fixed: offsets 8, 16, 32), then one atomic add per value
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-        ps[0][k] = y2_lane_group_sum<WCPR>(ps[0][k]);
-        ps[1][k] = y2_lane_group_sum<WCPR>(ps[1][k]);
-    }
-    // ... and the four wave rows of the workgroup (the same channels per column half) in LDS: a quarter of the atomic adds
+    // ---- the lanes that share a channel chunk meet (lane % 8 fixed), then the four wave rows of the workgroup (the same channels per column half) in LDS:
+    // one atomic add per value and workgroup, into row blockIdx.x % D1_STAT_ROWS (never unique: workgroups of every column group wrap around the rows)
+    bw.template lane_group_sum<WCPR>();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();                                       // every wave is done with the operand buffers
-    float *const red = reinterpret_cast<float *>(ab);
-    if (lane < WCPR) {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) { red[(wave * WCPR + lane) * 2 * VEC + k] = ps[0][k]; red[(wave * WCPR + lane) * 2 * VEC + VEC + k] = ps[1][k]; }
-    }
-    __syncthreads();
-    if (wm == 0 && lane < WCPR) {
-#pragma unroll
-        for (int r = 1; r < 4; ++r)
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) {
-                ps[0][k] += red[((2 * r + wn) * WCPR + lane) * 2 * VEC + k];
-                ps[1][k] += red[((2 * r + wn) * WCPR + lane) * 2 * VEC + VEC + k];
-            }
-        const int slot = (int)(blockIdx.x & (D1_STAT_ROWS - 1));
-        float *p1 = bn_part + (long)slot * Nf + nb, *p2 = bn_part + (long)(Y2_BN_PART_ROWS + slot) * Nf + nb;
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) { unsafeAtomicAdd(p1 + k, ps[0][k]); unsafeAtomicAdd(p2 + k, ps[1][k]); }
-    }
+    const bool writer = wm == 0 && lane < WCPR;
+    y2_wave_rows_meet<4, 2, WCPR>(reinterpret_cast<float *>(ab), wave, wn, lane, writer, bw.ps);
+    if (writer) Y2PartRows::of(bn_part, Nf, (Y2_BN_PART_ROWS - 1) ^ (D1_STAT_ROWS - 1)).publish((int)blockIdx.x, nb, bw.ps);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 

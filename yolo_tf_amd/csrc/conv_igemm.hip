@@ -51,6 +51,7 @@
 //     when the filter operand is small, one contiguous run of M tiles per XCD (halo rows shared in L2).
 #include "common.h"
 #include "conv_shared.h"
+#include "conv_epilogue.h"
 #include <stdlib.h>
 #include <atomic>
 #include <mutex>
@@ -84,20 +85,20 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(
     const float *__restrict__ bn_shift, float *__restrict__ bn_part, unsigned *__restrict__ sk_flags, float act_alpha, int wide_store,
     const Y2BnBwd bz) {
     constexpr int BM = BMv;                // pixels per tile: 128, or 256 (8 waves of 64 x 64)
+    typedef Y2IgemmPlan<T, BM, BN, WGN, NSTAGE, CH, NW> Plan;      // (conv_shared.h: the sizes the host counts partial rows from)
     constexpr int TAPS = KS * KS;
-    constexpr int VEC = 16 / sizeof(T);
+    constexpr int VEC = Plan::VEC;
     constexpr int BK = CH * VEC;           // CH = 16-byte chunks per tile row: 4 -> 32 bf16 / 16 f32 per K step
-    constexpr int ROWB = CH * 16;          // bytes per tile row
+    constexpr int ROWB = Plan::ROWB;       // bytes per tile row
     constexpr int RPL = 256 / ROWB;        // rows per 256-byte LDS bank line
-    constexpr int RPI = 64 / CH;           // rows per DMA instruction (1 KiB)
-    constexpr int WGM = NW / WGN;          // NW waves per workgroup, arranged WGM x WGN over the output tile
-    constexpr int TM = BM / WGM / 32, TN = BN / WGN / 32;
+    constexpr int RPI = Plan::RPI;         // rows per DMA instruction (1 KiB)
+    constexpr int WGM = Plan::WGM, TM = Plan::TM, TN = Plan::TN;      // waves WGM x WGN over the output tile, TM x TN MFMA blocks each
     constexpr int A_IT = BM / RPI / NW;    // DMA instructions per wave per tile
     constexpr int B_PIECES = BN / RPI;
-    constexpr int B_IT = (B_PIECES + NW - 1) / NW;
+    constexpr int B_IT = Plan::B_IT;
     constexpr int LOADS = A_IT + B_IT;   // counted on vmcnt; identical in every wave (idle B slots still issue, all-OOB)
     constexpr int PAD = KS / 2;
-    constexpr int STAGE = (BM + B_IT * NW * RPI) * ROWB;
+    constexpr int STAGE = Plan::STAGE;
     static_assert(A_IT >= 1, "at least one A piece per wave");
     static_assert(NSTAGE >= 2 && NSTAGE <= 4 && TM >= 1 && TN >= 1, "tile");
 
@@ -379,10 +380,8 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(
     // statistics pass over y (a full re-read of every activation, 21 launches per step) is gone.
     const bool stats = !BNBWD && SPLITK != 1 && bn_part != nullptr;
     const bool bstats = BNBWD && SPLITK != 1 && bn_part != nullptr;      // (host: only with the wide-store epilogue below)
-    // The partial rows are indexed by (pixel tile, wave row).  When those fit the 256 rows every (row, filter) has exactly one writer:
-    // plain stores, bitwise-reproducible statistics -- and the f32 atomics of the 13x13 stages (each a fabric round trip) were 10 us of
-    // a 77 us launch (profiles/r02_igemm_ablation.txt).  Larger layers wrap around the rows and keep the atomic adds.
-    const bool stats_unique = bz.stat_mask_inv == 0;       // the host found a row for every (pixel tile, wave row) pair
+    // The partial rows are indexed by (pixel tile, wave row); plain stores when the host found a row for every pair (conv_epilogue.h Y2PartRows)
+    const Y2PartRows part_rows = Y2PartRows::of(bn_part, Nf, bz.stat_mask_inv);
     auto write_tile = [&](auto checked_tag) {      // interior tiles skip the per-element row test (one VALU compare + branch each)
         constexpr bool CHECKED = decltype(checked_tag)::value;
 #pragma unroll
@@ -415,12 +414,7 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(
             if (stats) {      // lanes l and l^32 hold the same column (both pass the n < Nf test together)
                 s1 += __shfl_xor(s1, 32, 64);
                 s2 += __shfl_xor(s2, 32, 64);
-                if (lane < 32) {
-                    const int slot = (mt * WGM + wm) & ((Y2_BN_PART_ROWS - 1) ^ bz.stat_mask_inv);
-                    float *p1 = bn_part + (long)slot * Nf + n, *p2 = bn_part + (long)(Y2_BN_PART_ROWS + slot) * Nf + n;
-                    if (stats_unique) { *p1 = s1; *p2 = s2; }
-                    else { unsafeAtomicAdd(p1, s1); unsafeAtomicAdd(p2, s2); }
-                }
+                if (lane < 32) part_rows.publish(mt * Plan::STAT_ROWS_FWD + wm, n, s1, s2);
             }
         }
     };
@@ -430,8 +424,8 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(
     // sub-tile into a private, padded LDS image (the DMA ring is idle by now), computes the statistics from the rounded values
     // on the way, and reads it back row-major: 16 bytes (8 bf16 / 4 f32 consecutive filters of one pixel) per lane per store.
     {
-    constexpr int WROWS = TM * 32, WROWB = TN * 32 * (int)sizeof(T), WSTRIDE = WROWB + 16, WCPR = WROWB / 16;
-    constexpr bool WIDE_FITS = SPLITK != 1 && NW * WROWS * WSTRIDE <= NSTAGE * STAGE;
+    constexpr int WROWS = Plan::WROWS, WSTRIDE = Plan::WSTRIDE, WCPR = Plan::WCPR;
+    constexpr bool WIDE_FITS = SPLITK != 1 && Plan::WIDE_FITS;
     if (WIDE_FITS && wide_store) {
         // producer-layer operands of the fused BN-backward sums: this lane's VEC per-channel constants and the y vectors of the NIT
         // (pixel, chunk) positions it stores below -- all issued back to back, consumed after the staging loop (one exposed latency per
@@ -439,7 +433,7 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(
         constexpr int NIT = WROWS * WCPR / 64;
         constexpr int YG = NIT < 4 ? NIT : 4;       // y vectors in flight per lane (the 256-pixel tile spills with all 8)
         constexpr bool BZ_EARLY = SPLITK == 2 && BM == 128;
-        float cmu[VEC], cinv[VEC], cga[VEC], cbt[VEC], ps[2][VEC];
+        Y2BnBwdLane<T> bw;
         Vec16<T> yv[YG];
         const int bz_nb = min(n0 + wn * TN * 32 + (lane % WCPR) * VEC, Nf - VEC);      // (clamped: out-of-range chunks are never summed)
         auto bz_load_y = [&](int it0) {
@@ -451,19 +445,7 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(
         };
         auto bz_prefetch = [&]() {
             bz_load_y(0);
-#pragma unroll
-            for (int k = 0; k < VEC; k += 4) {
-                const f32x4 a = *reinterpret_cast<const f32x4 *>(bz.mean + bz_nb + k), b = *reinterpret_cast<const f32x4 *>(bz.var + bz_nb + k);
-                const f32x4 c = *reinterpret_cast<const f32x4 *>(bz.gamma + bz_nb + k), d = *reinterpret_cast<const f32x4 *>(bz.beta + bz_nb + k);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    cmu[k + q] = a[q];
-                    cinv[k + q] = 1.0f / sqrtf(b[q] + bz.eps);
-                    cga[k + q] = c[q];
-                    cbt[k + q] = d[q];
-                    ps[0][k + q] = ps[1][k + q] = 0.f;
-                }
-            }
+            bw.load(bz, bz_nb);
         };
         if (bstats && BZ_EARLY) bz_prefetch();
         __syncthreads();                       // every wave has finished reading the last K step's stage
@@ -495,12 +477,7 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(
             if (stats) {
                 s1 += __shfl_xor(s1, 32, 64);
                 s2 += __shfl_xor(s2, 32, 64);
-                if (lane < 32 && n_ok) {
-                    const int slot = (mt * WGM + wm) & ((Y2_BN_PART_ROWS - 1) ^ bz.stat_mask_inv);
-                    float *p1 = bn_part + (long)slot * Nf + n, *p2 = bn_part + (long)(Y2_BN_PART_ROWS + slot) * Nf + n;
-                    if (stats_unique) { *p1 = s1; *p2 = s2; }      // one writer per (row, filter): a store into the zeroed row
-                    else { unsafeAtomicAdd(p1, s1); unsafeAtomicAdd(p2, s2); }
-                }
+                if (lane < 32 && n_ok) part_rows.publish(mt * Plan::STAT_ROWS_FWD + wm, n, s1, s2);
             }
         }
         // (LDS operations of one wave execute in order: its own reads below see its own writes above)
@@ -508,72 +485,23 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_kernel(
         static_assert(64 % WCPR == 0, "a lane stays on one column chunk");
         if (bstats && !BZ_EARLY) bz_prefetch();
 #pragma unroll
-        for (int it = 0; it < WROWS * WCPR / 64; ++it) {
-            const int id = it * 64 + lane;
-            const int row = id / WCPR, ch = id % WCPR;
-            const int m = m0 + wm * WROWS + row;
-            const int n = n0 + wn * TN * 32 + ch * VEC;
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(wreg + row * WSTRIDE + ch * 16);
-            if (bstats && it && it % YG == 0) bz_load_y(it);
-            if (m < M && n < Nf) {
-                *reinterpret_cast<f32x4 *>(O + (long)m * ldo + n) = v;
-                if (bstats) {      // same arithmetic as bn_bwd_reduce_kernel (elementwise.hip), on the rounded gradient just stored
-                    const Vec16<T> y = yv[it % YG];
-                    Vec16<T> d;
-                    d.v = __builtin_bit_cast(decltype(d.v), v);
-#pragma unroll
-                    for (int k = 0; k < VEC; ++k) {
-                        const float xh = (y.get(k) - cmu[k]) * cinv[k];
-                        const float z = (y.get(k) - cmu[k]) * (cinv[k] * cga[k]) + cbt[k];
-                        const float g = z >= 0.f ? d.get(k) : bz.alpha * d.get(k);
-                        ps[0][k] += g * xh;
-                        ps[1][k] += g;
-                    }
-                }
-            }
+        for (int it = 0; it < NIT; ++it) {
+            y2_store_chunk<WSTRIDE, WCPR>(wreg, it * 64 + lane, 0, O, ldo, m0 + wm * WROWS, M, n0 + wn * TN * 32, Nf, bstats, bw, bz, yv[it % YG],
+                                          [&] { if (bstats && it && it % YG == 0) bz_load_y(it); });      // (the next YG y vectors, behind this LDS read)
         }
         if (bstats) {
-            // (the lanes that share a channel chunk meet on the VALU: common.h y2_lane_group_sum)
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) {
-                ps[0][k] = y2_lane_group_sum<WCPR>(ps[0][k]);
-                ps[1][k] = y2_lane_group_sum<WCPR>(ps[1][k]);
-            }
-            // The WGM wave rows of the tile hold sums of the SAME channels.  Where the LDS plan leaves room behind the tile image they meet there and the
-            // tile leaves ONE partial row per filter (the host counts rows per pixel tile then: y2_bnbwd_rows_per_tile) -- a WGM-th of the adds and of
-            // the (tile, wave row) pairs competing for the partial rows: same-address f32 atomics serialise at ~0.1 us each
-            constexpr bool RED = BNBWD && WGM > 1 && NW * WROWS * WSTRIDE + NW * WCPR * 2 * VEC * 4 <= NSTAGE * STAGE;
+            bw.template lane_group_sum<WCPR>();
+            // Where the LDS plan leaves room behind the tile images the WGM wave rows meet there and the tile leaves ONE partial row per filter
+            // (Plan::STAT_ROWS_BNBWD: what the host counts)
+            constexpr bool RED = BNBWD && Plan::RED;
+            static_assert(!BNBWD || Plan::STAT_ROWS_BNBWD == (RED ? 1 : WGM), "the host counts the rows this epilogue writes");
             const int nb = n0 + wn * TN * 32 + lane * VEC;
             bool writer = lane < WCPR && nb < Nf;
-            int row_id = mt * WGM + wm;
             if constexpr (RED) {
-                float *const red = reinterpret_cast<float *>(smem + NW * WROWS * WSTRIDE);
-                if (lane < WCPR) {
-#pragma unroll
-                    for (int k = 0; k < VEC; ++k) { red[(wave * WCPR + lane) * 2 * VEC + k] = ps[0][k]; red[(wave * WCPR + lane) * 2 * VEC + VEC + k] = ps[1][k]; }
-                }
-                __syncthreads();
                 writer = writer && wm == 0;
-                row_id = mt;
-                if (writer) {
-#pragma unroll
-                    for (int r = 1; r < WGM; ++r)
-#pragma unroll
-                        for (int k = 0; k < VEC; ++k) {
-                            ps[0][k] += red[((r * WGN + wn) * WCPR + lane) * 2 * VEC + k];
-                            ps[1][k] += red[((r * WGN + wn) * WCPR + lane) * 2 * VEC + VEC + k];
-                        }
-                }
+                y2_wave_rows_meet<WGM, WGN, WCPR>(reinterpret_cast<float *>(smem + Plan::IMAGES), wave, wn, lane, writer, bw.ps);
             }
-            if (writer) {
-                const int slot = row_id & ((Y2_BN_PART_ROWS - 1) ^ bz.stat_mask_inv);
-                float *p1 = bn_part + (long)slot * Nf + nb, *p2 = bn_part + (long)(Y2_BN_PART_ROWS + slot) * Nf + nb;
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) {
-                    if (stats_unique) { p1[k] = ps[0][k]; p2[k] = ps[1][k]; }
-                    else { unsafeAtomicAdd(p1 + k, ps[0][k]); unsafeAtomicAdd(p2 + k, ps[1][k]); }
-                }
-            }
+            if (writer) part_rows.publish(mt * Plan::STAT_ROWS_BNBWD + (RED ? 0 : wm), nb, bw.ps);
         }
     } else if (m0 + BM <= M) write_tile(std::false_type{});
     else write_tile(std::true_type{});
@@ -777,12 +705,14 @@ extern "C" int yolo2_last_bn_part_rows(void) { return g_last_stat_rows; }
         const dim3 g_ = (gridv);                                                                                   \
         const int plan_[8] = {BMv, BNv, NWv, CHv, NSv, SPLITv, (int)g_.x, (int)g_.y};                              \
         for (int i_ = 0; i_ < 8; ++i_) g_last_plan[i_] = plan_[i_];                                                \
-        const bool fusedbw_ = bz.Y && SPLITv != 1 && !CTv && wide_store && igemm_wide_fits<T, BMv, BNv, WGNv, NSv, CHv, NWv>();                      \
-        const Y2BnBwd bz_ = y2_with_stat_rows(bz, (long)cdiv(M, BMv) * (fusedbw_ ? y2_bnbwd_rows_per_tile<T, BMv, BNv, WGNv, NSv, CHv, NWv>() : (NWv / WGNv)), Nf, VEC); \
+        typedef Y2IgemmPlan<T, BMv, BNv, WGNv, NSv, CHv, NWv> Plan_;      /* the kernel's own LDS / tile plan (conv_shared.h) */ \
+        /* does this instantiation have the fused BN-backward epilogue? */                                         \
+        const bool fusedbw_ = bz.Y && SPLITv != 1 && !CTv && wide_store && Plan_::WIDE_FITS;                       \
+        const Y2BnBwd bz_ = y2_with_stat_rows(bz, (long)cdiv(M, BMv) * (fusedbw_ ? Plan_::STAT_ROWS_BNBWD : Plan_::STAT_ROWS_FWD), Nf, VEC); \
         if (!bz.Y)                                                                                                 \
             conv_igemm_kernel<T, BNv, WGNv, NSv, KSv, SPLITv, CTv, CHv, NWv, BMv, false><<<g_, NWv * 64, 0, st>>>(  \
                 Y2_IGEMM_ARGS, bn_part, sk_flags, act_alpha, wide_store, bz_);                                     \
-        else if (SPLITv != 1 && !CTv && wide_store && igemm_wide_fits<T, BMv, BNv, WGNv, NSv, CHv, NWv>())         \
+        else if (fusedbw_)                                                                                         \
             conv_igemm_kernel<T, BNv, WGNv, NSv, KSv, (SPLITv == 1 ? 0 : SPLITv), false, CHv, NWv, BMv, true><<<g_, NWv * 64, 0, st>>>( \
                 Y2_IGEMM_ARGS, bn_part, sk_flags, act_alpha, wide_store, bz_);                                     \
         else {      /* this variant has no on-chip tile image to reduce from: the caller runs the two-step form */ \
@@ -808,22 +738,6 @@ extern "C" int yolo2_last_bn_part_rows(void) { return g_last_stat_rows; }
         if (ksize == 3) Y2_IGEMM(128, 2, 3, 3, SPLITv, false, 8, 8, gridv);            \
         else Y2_IGEMM(128, 2, 3, 1, SPLITv, false, 8, 8, gridv);                       \
     } while (0)
-
-// partial rows one tile of a BN-backward instantiation writes: 1 when its wave rows meet in LDS (mirror of RED in the kernel), else one per wave row
-template <typename T, int BMv, int BN, int WGN, int NSTAGE, int CH, int NW>
-static constexpr int y2_bnbwd_rows_per_tile() {
-    constexpr int RPI = 64 / CH, ROWB = CH * 16, WGM = NW / WGN, TM = BMv / WGM / 32, TN = BN / WGN / 32, VEC = 16 / (int)sizeof(T);
-    constexpr int B_IT = (BN / RPI + NW - 1) / NW, STAGE = (BMv + B_IT * NW * RPI) * ROWB;
-    constexpr int WROWS = TM * 32, WROWB = TN * 32 * (int)sizeof(T), WSTRIDE = WROWB + 16, WCPR = WROWB / 16;
-    return (WGM > 1 && NW * WROWS * WSTRIDE + NW * WCPR * 2 * VEC * 4 <= NSTAGE * STAGE) ? 1 : WGM;
-}
-// does this instantiation have the LDS-transposed (wide-store) epilogue?  (mirror of WIDE_FITS in the kernel)
-template <typename T, int BMv, int BN, int WGN, int NSTAGE, int CH, int NW>
-static constexpr bool igemm_wide_fits() {
-    constexpr int RPI = 64 / CH, ROWB = CH * 16, WGM = NW / WGN, TM = BMv / WGM / 32, TN = BN / WGN / 32;
-    constexpr int B_IT = (BN / RPI + NW - 1) / NW, STAGE = (BMv + B_IT * NW * RPI) * ROWB;
-    return NW * (TM * 32) * (TN * 32 * (int)sizeof(T) + 16) <= NSTAGE * STAGE;
-}
 
 // tap-fused 3x3 variant on/off (default: env YOLO2_IGEMM_TAP, else on); yolo2_debug_set_igemm_tap flips it at run time so that
 // tests can compare both variants on the same inputs
@@ -947,9 +861,9 @@ static int launch_conv(const void *P, const void *F, const float *bias, void *O,
             if (grid > 0 && (sk_flags = stream_flags()) != nullptr) {
                 const int plan_[8] = {256, 128, 8, 8, 18, 2, grid, 1};      // "stages" 18: nine taps per halo image, two phases per tap
                 for (int i_ = 0; i_ < 8; ++i_) g_last_plan[i_] = plan_[i_];
-                // partial rows: forward statistics one per (pixel tile, wave row); BN-backward sums of the ping-pong kernel one per pixel tile (its wave
-                // rows meet in LDS); the loader / consumer kernel one per (pixel tile, 64-row group)
-                const Y2BnBwd bz_ = y2_with_stat_rows(bz, (bz.Y && tap_mode != 3) ? (long)MT2 : (long)MT2 * 4, Nf, VEC);
+                // partial rows per pixel tile: what the kernel that runs indexes (conv_shared.h)
+                const int tile_rows = tap_mode == 3 ? (bz.Y ? Y2S_STAT_ROWS_BNBWD : Y2S_STAT_ROWS_FWD) : (bz.Y ? Y2P_STAT_ROWS_BNBWD : Y2P_STAT_ROWS_FWD);
+                const Y2BnBwd bz_ = y2_with_stat_rows(bz, (long)MT2 * tile_rows, Nf, VEC);
                 // owner cost of the cost-balanced partition: below half a workgroup's share, so that every workgroup keeps real K steps (an owner
                 // waits for the flag of every workgroup inside its tile); whole-tile grids have no shares to balance
                 int cv = grid == tiles_t ? 0 : g_pp_cv.load(std::memory_order_relaxed);

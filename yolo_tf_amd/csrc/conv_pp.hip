@@ -28,6 +28,7 @@
 //   * One fragment register set (64 VGPRs) instead of two: ~170 VGPRs.
 #include "common.h"
 #include "conv_shared.h"
+#include "conv_epilogue.h"
 #include <type_traits>
 
 #define Y2P_BM 256
@@ -544,11 +545,12 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(
     {
         const bool stats = !BNBWD && bn_part != nullptr;
         const bool bstats = BNBWD && bn_part != nullptr;
-        const bool stats_unique = bz.stat_mask_inv == 0;       // the host found a row for every (pixel tile, wave_e row) pair
+        const Y2PartRows part_rows = Y2PartRows::of(bn_part, Nf, bz.stat_mask_inv);       // (unique when the host found a row for every (pixel tile, wave_e row) pair)
+        static_assert(Y2P_STAT_ROWS_FWD == WGM && Y2P_STAT_ROWS_BNBWD == 1, "the host counts the partial rows a pixel tile writes (conv_shared.h)");
         constexpr int WROWS = TM * 32, WROWB = TN * 32 * 2, WSTRIDE = WROWB + 16, WCPR = WROWB / 16, NIT = WROWS * WCPR / 64, YG = 4;
         static_assert(NW * WROWS * WSTRIDE <= RING, "tile image fits the halo buffers");
         static_assert(NW * WROWS * WSTRIDE <= HB + HBYTES, "the idle-DMA sink (zero KiB of halo buffer 1) lies behind the tile image");
-        float cmu[VEC], cinv[VEC], cga[VEC], cbt[VEC], ps[2][VEC];
+        Y2BnBwdLane<T> bw;
         Vec16<T> yv[YG];
         const int bz_nb = min(n0 + wn_e * TN * 32 + (lane_e % WCPR) * VEC, Nf - VEC);
         auto bz_load_y = [&](int it0) {
@@ -574,43 +576,12 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(
         Y2P_STAMP(5);
         unsigned char *wreg = smem + wave_e * (WROWS * WSTRIDE);
         const bool tail = m0 + BM > M;
-        // Staging: rounded tile into this wave's LDS image (+ the statistics of the rounded values).  Two copies of the 64-element loop,
-        // chosen by ONE uniform branch: the leaky ReLU of a BN-folded inference layer and the row test of the last pixel tile each cost
-        // two to three VALU per element when they are tested inside it (~10 % of the ~7 us a tile's epilogue takes).
+        // Staging (conv_epilogue.h y2_stage_column): four specialised copies of the 64-element loop, chosen by ONE uniform branch
         auto stage_tile = [&](auto act_tag, auto tail_tag) {
-            constexpr bool ACT = decltype(act_tag)::value, TAIL = decltype(tail_tag)::value;
 #pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const float bv = bvj[j], sh = shj[j];
-                float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int row = i * 32 + 4 * (lane_e >> 5) + (r & 3) + 8 * (r >> 2);
-                        float v = acc[i][j][r] + bv;
-                        if (ACT) v = fmaxf(v, act_alpha * v);
-                        const T o = (T)v;
-                        *reinterpret_cast<T *>(wreg + row * WSTRIDE + (j * 32 + (lane_e & 31)) * 2) = o;
-                        if (stats && (!TAIL || m0 + wm_e * WROWS + row < M)) {
-                            const float d = (float)o - sh;
-                            s1 += d;
-                            s2 += d * d;
-                        }
-                    }
-                }
-                if (stats) {
-                    s1 += __shfl_xor(s1, 32, 64);
-                    s2 += __shfl_xor(s2, 32, 64);
-                    if (lane_e < 32 && nokj[j]) {
-                        const int n = n0 + (wn_e * TN + j) * 32 + (lane_e & 31);
-                        const int slot = (mt * WGM + wm_e) & ((Y2_BN_PART_ROWS - 1) ^ bz.stat_mask_inv);
-                        float *p1 = bn_part + (long)slot * Nf + n, *p2 = bn_part + (long)(Y2_BN_PART_ROWS + slot) * Nf + n;
-                        if (stats_unique) { *p1 = s1; *p2 = s2; }
-                        else { unsafeAtomicAdd(p1, s1); unsafeAtomicAdd(p2, s2); }
-                    }
-                }
-            }
+            for (int j = 0; j < TN; ++j)
+                y2_stage_column<0, TM, WSTRIDE, T>(acc, j, wreg, lane_e, bvj[j], act_alpha, act_tag, tail_tag, m0 + wm_e * WROWS, M, stats, shj[j], part_rows,
+                                                   mt * Y2P_STAT_ROWS_FWD + wm_e, n0 + (wn_e * TN + j) * 32 + (lane_e & 31), nokj[j]);
         };
         if (act_alpha != 1.0f) { if (tail) stage_tile(std::true_type{}, std::true_type{}); else stage_tile(std::true_type{}, std::false_type{}); }
         else if (tail) stage_tile(std::false_type{}, std::true_type{});
@@ -621,19 +592,7 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(
             // loop, where the 64 accumulator registers are still live -- the BN-backward instantiations then need 245 .. 256+ registers)
             int nb_c = bz_nb;
             asm volatile("" : "+v"(nb_c));
-#pragma unroll
-            for (int k = 0; k < VEC; k += 4) {
-                const f32x4 a = *reinterpret_cast<const f32x4 *>(bz.mean + nb_c + k), b = *reinterpret_cast<const f32x4 *>(bz.var + nb_c + k);
-                const f32x4 c = *reinterpret_cast<const f32x4 *>(bz.gamma + nb_c + k), d = *reinterpret_cast<const f32x4 *>(bz.beta + nb_c + k);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    cmu[k + q] = a[q];
-                    cinv[k + q] = 1.0f / sqrtf(b[q] + bz.eps);
-                    cga[k + q] = c[q];
-                    cbt[k + q] = d[q];
-                    ps[0][k + q] = ps[1][k + q] = 0.f;
-                }
-            }
+            bw.load(bz, nb_c);
         }
         static_assert(NIT % YG == 0, "whole groups of y vectors");
         // (groups of YG rows, NOT unrolled across groups: fully unrolled, the eight iterations' loads were all hoisted to the top and the
@@ -642,64 +601,18 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(
         for (int g0 = 0; g0 < NIT; g0 += YG) {
             if (bstats && g0) bz_load_y(g0);
 #pragma unroll
-            for (int u = 0; u < YG; ++u) {
-                const int id = (g0 + u) * 64 + lane_e;
-                const int row = id / WCPR, ch = id % WCPR;
-                const int m = m0 + wm_e * WROWS + row;
-                const int n = n0 + wn_e * TN * 32 + ch * VEC;
-                const f32x4 v = *reinterpret_cast<const f32x4 *>(wreg + row * WSTRIDE + ch * 16);
-                if (m < M && n < Nf) {
-                    *reinterpret_cast<f32x4 *>(O + (long)m * ldo + n) = v;
-                    if (bstats) {
-                        const Vec16<T> y = yv[u];
-                        Vec16<T> d;
-                        d.v = __builtin_bit_cast(decltype(d.v), v);
-#pragma unroll
-                        for (int k = 0; k < VEC; ++k) {
-                            const float xh = (y.get(k) - cmu[k]) * cinv[k];
-                            const float z = (y.get(k) - cmu[k]) * (cinv[k] * cga[k]) + cbt[k];
-                            const float g = z >= 0.f ? d.get(k) : bz.alpha * d.get(k);
-                            ps[0][k] += g * xh;
-                            ps[1][k] += g;
-                        }
-                    }
-                }
-            }
+            for (int u = 0; u < YG; ++u)
+                y2_store_chunk<WSTRIDE, WCPR>(wreg, (g0 + u) * 64 + lane_e, 0, O, ldo, m0 + wm_e * WROWS, M, n0 + wn_e * TN * 32, Nf, bstats, bw, bz, yv[u]);
         }
         if (bstats) {
-            // (the lanes that share a channel chunk meet on the VALU: common.h y2_lane_group_sum)
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) {
-                ps[0][k] = y2_lane_group_sum<WCPR>(ps[0][k]);
-                ps[1][k] = y2_lane_group_sum<WCPR>(ps[1][k]);
-            }
-            // The four wave rows of the tile hold sums of the SAME channels: they meet in LDS (the 7 KiB between the tile image and the idle-DMA sink) and
-            // the tile leaves ONE partial row per filter -- a quarter of the adds, and at most 169 pixel tiles instead of 676 (tile, wave row) pairs
-            // competing for the partial rows: same-address f32 atomics were 12 us of the 52 x 52 launch's 52 (profiles/r06_pp_bn_epilogue.txt)
+            bw.template lane_group_sum<WCPR>();
+            // the four wave rows meet in LDS (the 7 KiB between the tile image and the idle-DMA sink): ONE partial row per pixel tile and filter -- at most 169
+            // pixel tiles instead of 676 (tile, wave row) pairs competing for the partial rows
             static_assert(NW * WROWS * WSTRIDE + NW * WCPR * 2 * VEC * 4 <= HB + HBYTES, "reduction scratch fits between the tile image and the sink");
-            float *const red = reinterpret_cast<float *>(smem + NW * WROWS * WSTRIDE);
-            if (lane_e < WCPR) {
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) { red[(wave_e * WCPR + lane_e) * 2 * VEC + k] = ps[0][k]; red[(wave_e * WCPR + lane_e) * 2 * VEC + VEC + k] = ps[1][k]; }
-            }
-            __syncthreads();
             const int nb = n0 + wn_e * TN * 32 + lane_e * VEC;
-            if (wm_e == 0 && lane_e < WCPR && nb < Nf) {
-#pragma unroll
-                for (int r = 1; r < WGM; ++r)
-#pragma unroll
-                    for (int k = 0; k < VEC; ++k) {
-                        ps[0][k] += red[((r * WGN + wn_e) * WCPR + lane_e) * 2 * VEC + k];
-                        ps[1][k] += red[((r * WGN + wn_e) * WCPR + lane_e) * 2 * VEC + VEC + k];
-                    }
-                const int slot = mt & ((Y2_BN_PART_ROWS - 1) ^ bz.stat_mask_inv);
-                float *p1 = bn_part + (long)slot * Nf + nb, *p2 = bn_part + (long)(Y2_BN_PART_ROWS + slot) * Nf + nb;
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) {
-                    if (stats_unique) { p1[k] = ps[0][k]; p2[k] = ps[1][k]; }
-                    else { unsafeAtomicAdd(p1 + k, ps[0][k]); unsafeAtomicAdd(p2 + k, ps[1][k]); }
-                }
-            }
+            const bool writer = wm_e == 0 && lane_e < WCPR && nb < Nf;
+            y2_wave_rows_meet<WGM, WGN, WCPR>(reinterpret_cast<float *>(smem + NW * WROWS * WSTRIDE), wave_e, wn_e, lane_e, writer, bw.ps);
+            if (writer) part_rows.publish(mt * Y2P_STAT_ROWS_BNBWD, nb, bw.ps);
         }
         Y2P_STAMP(7);
         // the idle DMA slots have landed before this workgroup's LDS is reused (next segment) or released (kernel end); the output stores ride along

@@ -21,6 +21,7 @@
 //     rows (and reduce the BN-backward sums) -- the loaders take half of every image.
 #include "common.h"
 #include "conv_shared.h"
+#include "conv_epilogue.h"
 #include <type_traits>
 
 #define Y2S_BM 256
@@ -420,7 +421,9 @@ __global__ __launch_bounds__(512) void conv3x3_s4_kernel(
     {
         const bool stats = !BNBWD && bn_part != nullptr;
         const bool bstats = BNBWD && bn_part != nullptr;
-        const bool stats_unique = bz.stat_mask_inv == 0;       // the host found a row for every (pixel tile, 64-row group) pair
+        const Y2PartRows part_rows = Y2PartRows::of(bn_part, Nf, bz.stat_mask_inv);       // (unique when the host found a row for every (pixel tile, 64-row group) pair)
+        // the statistics rows are per 64 pixel rows: (pixel tile, wm, half) -> one partial row
+        static_assert(Y2S_STAT_ROWS_FWD == WGM * 2 && Y2S_STAT_ROWS_BNBWD == WGM * 2, "the host counts the partial rows a pixel tile writes (conv_shared.h)");
         constexpr int WROWS = TM * 32, WROWB = TN * 32 * 2, WSTRIDE = WROWB + 16, WCPR = WROWB / 16, HROWS_W = WROWS / 2, NIT = HROWS_W * WCPR / 64, YG = 4;
         static_assert(NCW * WROWS * WSTRIDE <= RING && NCW * WROWS * WSTRIDE <= HB + HBYTES, "tile image fits the halo buffers, in front of the idle-DMA sink");
         __syncthreads();                                      // every compute wave has finished reading the last step's operands (idle DMA slots write behind the image)
@@ -438,41 +441,13 @@ __global__ __launch_bounds__(512) void conv3x3_s4_kernel(
             }
             const bool tail = m0 + BM > M;
             auto stage_tile = [&](auto act_tag, auto tail_tag) {
-                constexpr bool ACT = decltype(act_tag)::value, TAIL = decltype(tail_tag)::value;
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
-                    const float bv = bvj[j], sh = shj[j];
-#pragma unroll
-                    for (int hf = 0; hf < 2; ++hf) {          // the statistics rows are per 64 pixel rows: (pixel tile, wm, half) -> one partial row
-                        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-                        for (int i = 2 * hf; i < 2 * hf + 2; ++i) {
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) {
-                                const int row = i * 32 + 4 * (lane_e >> 5) + (r & 3) + 8 * (r >> 2);
-                                float v = acc[i][j][r] + bv;
-                                if (ACT) v = fmaxf(v, act_alpha * v);
-                                const T o = (T)v;
-                                *reinterpret_cast<T *>(wreg + row * WSTRIDE + (j * 32 + (lane_e & 31)) * 2) = o;
-                                if (stats && (!TAIL || m0 + wm_e * WROWS + row < M)) {
-                                    const float d = (float)o - sh;
-                                    s1 += d;
-                                    s2 += d * d;
-                                }
-                            }
-                        }
-                        if (stats) {
-                            s1 += __shfl_xor(s1, 32, 64);
-                            s2 += __shfl_xor(s2, 32, 64);
-                            if (lane_e < 32 && nokj[j]) {
-                                const int n = n0 + (wn_e * TN + j) * 32 + (lane_e & 31);
-                                const int slot = (mt * 4 + wm_e * 2 + hf) & ((Y2_BN_PART_ROWS - 1) ^ bz.stat_mask_inv);
-                                float *p1 = bn_part + (long)slot * Nf + n, *p2 = bn_part + (long)(Y2_BN_PART_ROWS + slot) * Nf + n;
-                                if (stats_unique) { *p1 = s1; *p2 = s2; }
-                                else { unsafeAtomicAdd(p1, s1); unsafeAtomicAdd(p2, s2); }
-                            }
-                        }
-                    }
+                    const int n = n0 + (wn_e * TN + j) * 32 + (lane_e & 31), row_id = mt * Y2S_STAT_ROWS_FWD + wm_e * 2;
+                    y2_stage_column<0, TM / 2, WSTRIDE, T>(acc, j, wreg, lane_e, bvj[j], act_alpha, act_tag, tail_tag, m0 + wm_e * WROWS, M, stats, shj[j], part_rows,
+                                                           row_id, n, nokj[j]);
+                    y2_stage_column<TM / 2, TM, WSTRIDE, T>(acc, j, wreg, lane_e, bvj[j], act_alpha, act_tag, tail_tag, m0 + wm_e * WROWS, M, stats, shj[j], part_rows,
+                                                            row_id + 1, n, nokj[j]);
                 }
             };
             if (act_alpha != 1.0f) { if (tail) stage_tile(std::true_type{}, std::true_type{}); else stage_tile(std::true_type{}, std::false_type{}); }
@@ -483,7 +458,7 @@ __global__ __launch_bounds__(512) void conv3x3_s4_kernel(
         Y2S_STAMP(6);
         // ---- store loop: this wave takes rows [hrow0, hrow0 + 64) of image cw_e
         const int hrow0 = comp_e ? 0 : HROWS_W;
-        float cmu[VEC], cinv[VEC], cga[VEC], cbt[VEC], ps[2][VEC];
+        Y2BnBwdLane<T> bw;
         Vec16<T> yv[YG];
         const int bz_nb = min(n0 + wn_e * TN * 32 + (lane_e % WCPR) * VEC, Nf - VEC);
         auto bz_load_y = [&](int it0) {
@@ -497,67 +472,26 @@ __global__ __launch_bounds__(512) void conv3x3_s4_kernel(
             bz_load_y(0);
             int nb_c = bz_nb;
             asm volatile("" : "+v"(nb_c));
-#pragma unroll
-            for (int k = 0; k < VEC; k += 4) {
-                const f32x4 a = *reinterpret_cast<const f32x4 *>(bz.mean + nb_c + k), b = *reinterpret_cast<const f32x4 *>(bz.var + nb_c + k);
-                const f32x4 c = *reinterpret_cast<const f32x4 *>(bz.gamma + nb_c + k), d = *reinterpret_cast<const f32x4 *>(bz.beta + nb_c + k);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    cmu[k + q] = a[q];
-                    cinv[k + q] = 1.0f / sqrtf(b[q] + bz.eps);
-                    cga[k + q] = c[q];
-                    cbt[k + q] = d[q];
-                    ps[0][k + q] = ps[1][k + q] = 0.f;
-                }
-            }
+            bw.load(bz, nb_c);
         }
         static_assert(NIT % YG == 0, "whole groups of y vectors");
 #pragma unroll 1
         for (int g0 = 0; g0 < NIT; g0 += YG) {
             if (bstats && g0) bz_load_y(g0);
 #pragma unroll
-            for (int u = 0; u < YG; ++u) {
-                const int id = (g0 + u) * 64 + lane_e;
-                const int row = hrow0 + id / WCPR, ch = id % WCPR;
-                const int m = m0 + wm_e * WROWS + row;
-                const int n = n0 + wn_e * TN * 32 + ch * VEC;
-                const f32x4 v = *reinterpret_cast<const f32x4 *>(wreg + row * WSTRIDE + ch * 16);
-                if (m < M && n < Nf) {
-                    *reinterpret_cast<f32x4 *>(O + (long)m * ldo + n) = v;
-                    if (bstats) {
-                        const Vec16<T> y = yv[u];
-                        Vec16<T> d;
-                        d.v = __builtin_bit_cast(decltype(d.v), v);
-#pragma unroll
-                        for (int k = 0; k < VEC; ++k) {
-                            const float xh = (y.get(k) - cmu[k]) * cinv[k];
-                            const float z = (y.get(k) - cmu[k]) * (cinv[k] * cga[k]) + cbt[k];
-                            const float g = z >= 0.f ? d.get(k) : bz.alpha * d.get(k);
-                            ps[0][k] += g * xh;
-                            ps[1][k] += g;
-                        }
-                    }
-                }
-            }
+            for (int u = 0; u < YG; ++u)
+                y2_store_chunk<WSTRIDE, WCPR>(wreg, (g0 + u) * 64 + lane_e, hrow0, O, ldo, m0 + wm_e * WROWS, M, n0 + wn_e * TN * 32, Nf, bstats, bw, bz, yv[u]);
         }
         if (bstats) {
 #pragma unroll
             for (int off = WCPR; off < 64; off <<= 1)
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) {
-                    ps[0][k] += __shfl_xor(ps[0][k], off, 64);
-                    ps[1][k] += __shfl_xor(ps[1][k], off, 64);
+                    bw.ps[0][k] += __shfl_xor(bw.ps[0][k], off, 64);
+                    bw.ps[1][k] += __shfl_xor(bw.ps[1][k], off, 64);
                 }
             const int nb = n0 + wn_e * TN * 32 + lane_e * VEC;
-            if (lane_e < WCPR && nb < Nf) {
-                const int slot = (mt * 4 + wm_e * 2 + (comp_e ? 0 : 1)) & ((Y2_BN_PART_ROWS - 1) ^ bz.stat_mask_inv);
-                float *p1 = bn_part + (long)slot * Nf + nb, *p2 = bn_part + (long)(Y2_BN_PART_ROWS + slot) * Nf + nb;
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) {
-                    if (stats_unique) { p1[k] = ps[0][k]; p2[k] = ps[1][k]; }
-                    else { unsafeAtomicAdd(p1 + k, ps[0][k]); unsafeAtomicAdd(p2 + k, ps[1][k]); }
-                }
-            }
+            if (lane_e < WCPR && nb < Nf) part_rows.publish(mt * Y2S_STAT_ROWS_BNBWD + wm_e * 2 + (comp_e ? 0 : 1), nb, bw.ps);
         }
         Y2S_STAMP(7);
         // the idle DMA slots have landed before this workgroup's LDS is reused (next segment) or released (kernel end); the output stores ride along

@@ -1,4 +1,5 @@
-// Declarations shared by the implicit-GEMM translation units (conv_igemm.hip, conv_pp.hip).
+// Declarations shared by the convolution translation units (conv_igemm.hip, conv_pp.hip, conv_s4.hip, conv_d1.hip, conv_c32.hip, conv_c64.hip,
+// conv_wgrad.hip, conv_wgrad3.hip, conv_wgrad_c32.hip) and the epilogue they share (conv_epilogue.h).
 #pragma once
 #include "common.h"
 
@@ -48,6 +49,31 @@ struct Y2BnBwd {
     // (yolo2_bn_leaky_fin & co.) reads few of them while same-address atomic adds stay rare (y2_stat_rows in conv_igemm.hip).  0 = all 256 rows.
     int stat_mask_inv;
 };
+
+// LDS / tile plan of one conv_igemm_kernel instantiation -- the ONE place its sizes are derived: the kernel takes its constants from here, and
+// the host (conv_igemm.hip Y2_IGEMM_BM) counts the partial rows a pixel tile writes from the same struct.
+template <typename T, int BM, int BN, int WGN, int NSTAGE, int CH, int NW> struct Y2IgemmPlan {
+    static constexpr int VEC = 16 / (int)sizeof(T);
+    static constexpr int ROWB = CH * 16;          // bytes per tile row (CH 16-byte chunks)
+    static constexpr int RPI = 64 / CH;           // rows per DMA instruction (1 KiB)
+    static constexpr int WGM = NW / WGN;          // NW waves per workgroup, arranged WGM x WGN over the output tile
+    static constexpr int TM = BM / WGM / 32, TN = BN / WGN / 32;
+    static constexpr int B_IT = (BN / RPI + NW - 1) / NW;
+    static constexpr int STAGE = (BM + B_IT * NW * RPI) * ROWB, RING = NSTAGE * STAGE;
+    // wide-store epilogue: one padded image of WROWS rows x WCPR 16-byte chunks per wave, in the (idle) DMA ring
+    static constexpr int WROWS = TM * 32, WROWB = TN * 32 * (int)sizeof(T), WSTRIDE = WROWB + 16, WCPR = WROWB / 16;
+    static constexpr int IMAGES = NW * WROWS * WSTRIDE;
+    static constexpr bool WIDE_FITS = IMAGES <= RING;      // (K-sliced launches never take it)
+    // BN-backward sums: the wave rows of a tile meet in LDS where the ring leaves room behind the images (conv_epilogue.h y2_wave_rows_meet)
+    static constexpr bool RED = WGM > 1 && IMAGES + NW * WCPR * 2 * VEC * 4 <= RING;
+    // partial rows one pixel tile writes: forward statistics one per wave row; BN-backward sums one where the wave rows meet
+    static constexpr int STAT_ROWS_FWD = WGM, STAT_ROWS_BNBWD = RED ? 1 : WGM;
+};
+// ... of the fixed-tile kernels (256 pixels per tile).  conv_pp.hip: forward one row per wave row, BN-backward one per tile (its wave rows meet in
+// LDS); conv_s4.hip: one per 64-row group -- (wave row, half) -- in both forms; conv_d1.hip: one per workgroup, wrapped around D1_STAT_ROWS
+constexpr int Y2P_STAT_ROWS_FWD = 4, Y2P_STAT_ROWS_BNBWD = 1;
+constexpr int Y2S_STAT_ROWS_FWD = 4, Y2S_STAT_ROWS_BNBWD = 4;
+constexpr int D1_STAT_ROWS = 32;
 
 // conv_pp.hip: ping-pong tap-fused 3x3 kernel (bf16, 256 x 128 tile); returns non-zero when the image is too wide for its halo buffers
 int y2_conv3x3_pp_launch(const void *P, unsigned p_bytes, const void *F, unsigned f_bytes, const float *bias, void *O, float *ws, int H, int W, int Cp,
