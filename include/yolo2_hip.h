@@ -707,6 +707,32 @@ int yolo2_anchor_assign(const float *boxes, int n, const float *centroids, const
 int yolo2_anchor_update(float *centroids, const int *job_k, int jobs, int kmax, unsigned long long *ws, size_t ws_bytes, int n,
                         int *done, int *iterations, long long *counts, double *avg_iou, void *stream);
 
+/* ---- histogram summaries (new work): what the reference's train.py:44-60 asks tf.summary.histogram for, of many device tensors in
+ * one call.  Specification: tests/summary_ref.py (TensorFlow 1.x core/lib/histogram/histogram.cc restated; unpinned against TensorFlow).
+ * 1550 buckets: limits {-p reversed, 0, p, DBL_MAX} with p = 1e-12 * 1.1^i by repeated f64 multiplication while < 1e20 (774 values);
+ * a finite value x, widened exactly to f64, goes to bucket upper_bound(limits, x); NaN / +-inf are left out and counted.
+ *
+ * A job is one tensor: `rows` rows of `c` values with row stride `ld` elements (a flat range of n values: rows = 1, c = ld = n; rows = 0:
+ * an empty job), `dtype` YOLO2_F32 or YOLO2_BF16, `base` aligned to its element only.  Lanes c <= j < ld of a row are padding: whatever
+ * they hold never reaches the result (the bytes between base and the last row's last value must be readable).  `first_item` is the sum
+ * of yolo2_histogram_items() over the jobs before it; `items` of the call is that sum over all of them.  The job table lives in DEVICE memory.
+ * out [njobs][YOLO2_HIST_WORDS] 64-bit words per job: YOLO2_HIST_BUCKETS counts (u64), then min, max, sum, sum_squares (f64), then num,
+ * nonfinite (u64); an empty job reports min = DBL_MAX, max = -DBL_MAX.  Counts, num, nonfinite, min and max are exact; the sums are f64
+ * accumulations.  The whole record of a job is bitwise reproducible and depends on the job alone: no float atomic is issued.
+ * One call enqueues three operations whatever njobs is and never synchronises; ws needs no initialisation. */
+#define YOLO2_HIST_BUCKETS 1550
+#define YOLO2_HIST_WORDS (YOLO2_HIST_BUCKETS + 6)
+typedef struct yolo2_hist_job {
+    const void *base;
+    long long rows;
+    int c, ld, dtype;
+    int first_item;
+} yolo2_hist_job;
+size_t yolo2_histogram_workspace_bytes(int njobs);
+size_t yolo2_histogram_result_bytes(int njobs);                    /* njobs * YOLO2_HIST_WORDS * 8 */
+int yolo2_histogram_items(long long rows, int c, int ld, int dtype);   /* work items of one job (a count, not a status); 0 for an empty or malformed one */
+int yolo2_histogram(const yolo2_hist_job *jobs, int njobs, int items, void *out, size_t out_bytes, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@ from yolo_tf_amd import checkpoint, tf_checkpoint, utils
 from yolo_tf_amd.utils import events
 from yolo_tf_amd.parallel import agree, init_distributed, sync_replicas
 from yolo_tf_amd.session import TrainSession
+from yolo_tf_amd.summary import HistogramSummaries
 from yolo_tf_amd.utils import data as udata
 
 
@@ -186,6 +187,9 @@ def main():
         data = NpzData(args.data, args.batch_size, seed, rank, world)
     # the reference's summary_writer (train.py:141-145): scalar events under <logdir>/<logname>
     writer = events.FileWriter(os.path.join(logdir, args.logname)) if rank == 0 else None
+    # [summary] histogram / gradients (the reference's summary_histogram and summarize_gradients): rank 0 bins its own replica's tensors on the
+    # device after a summarised step; with both keys unset nothing is allocated or launched
+    histograms = HistogramSummaries(session, config) if rank == 0 else None
     save = (lambda: tf_checkpoint.save(logdir, session)) if args.ckpt_format == 'tf' else (lambda: checkpoint.save(logdir, session))
     last_summary = last_save = t_rate = time.time()
     n_rate = 0
@@ -213,6 +217,8 @@ def main():
         if bad_device:
             raise dev_error if dev_error is not None else RuntimeError('another rank reported a device-side failure (stream-K hand-off gave up)')
         if want_summary:
+            if histograms is not None and histograms.enabled:
+                histograms.collect()             # asynchronous: binned and copied behind the step, read after fetch() below
             s = session.fetch()
             shard_error = None
             if hasattr(data, 'pipe'):
@@ -226,6 +232,8 @@ def main():
             rate = n_rate * args.batch_size * world / (time.time() - t_rate)
             if rank == 0:
                 writer.add_training_summary(session.global_step, s)
+                if histograms.enabled:
+                    histograms.write(writer, session.global_step)
                 writer.flush()
                 logging.warning('step %d: total_loss=%.6f iou_best=%.6f iou_normal=%.6f coords=%.6f prob=%.6f (%.1f img/s)'
                                 % (session.global_step, s['total_loss'], s['iou_best'], s['iou_normal'], s['coords'], s['prob'], rate))

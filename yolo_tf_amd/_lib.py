@@ -108,6 +108,7 @@ SIGNATURES = {
     'yolo2_eval_coco_finalize': [_p, _l, _p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, ctypes.c_size_t, _p, _p],
     'yolo2_anchor_assign': [_p, _i, _p, _p, _i, _i, _p, ctypes.c_size_t, _p, _p, _p],
     'yolo2_anchor_update': [_p, _p, _i, _i, _p, ctypes.c_size_t, _i, _p, _p, _p, _p, _p],
+    'yolo2_histogram': [_p, _i, _i, _p, ctypes.c_size_t, _p, ctypes.c_size_t, _p],
 }
 
 # host queries / diagnostics: (restype, argtypes); bound in load() next to the status-returning entries above
@@ -152,6 +153,9 @@ QUERIES = {
     'yolo2_eval_coco_workspace_bytes': (ctypes.c_size_t, [_l, _i]),
     'yolo2_eval_coco_result_bytes': (ctypes.c_size_t, [_i, _i, _i, _i]),
     'yolo2_anchor_workspace_bytes': (ctypes.c_size_t, [_i, _i]),
+    'yolo2_histogram_workspace_bytes': (ctypes.c_size_t, [_i]),
+    'yolo2_histogram_result_bytes': (ctypes.c_size_t, [_i]),
+    'yolo2_histogram_items': (_i, [ctypes.c_longlong, _i, _i, _i]),        # a count, not a status
 }
 
 
@@ -160,6 +164,11 @@ class AugmentParams(ctypes.Structure):
     _fields_ = [('src_offset', ctypes.c_longlong), ('src_w', _i), ('src_h', _i), ('crop_x', _i), ('crop_y', _i), ('crop_w', _i), ('crop_h', _i),
                 ('flags', ctypes.c_uint), ('brightness', _f), ('saturation', _f), ('hue', _f), ('contrast', _f), ('noise_scale', _f),
                 ('noise_seed', ctypes.c_ulonglong)]
+
+
+class HistJob(ctypes.Structure):
+    """yolo2_hist_job of include/yolo2_hip.h"""
+    _fields_ = [('base', ctypes.c_void_p), ('rows', ctypes.c_longlong), ('c', _i), ('ld', _i), ('dtype', _i), ('first_item', _i)]
 
 
 class FilterDesc(ctypes.Structure):

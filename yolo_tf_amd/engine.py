@@ -982,3 +982,27 @@ class Engine(object):
 
     def output(self):
         return self.graph.ops[-1]['out']
+
+    def summarizable_tensors(self):
+        """Activations of the current binding for the histogram summaries (yolo_tf_amd/summary.py): [(tensor, (buffer, rows, c, ld) or None)].
+        None = the training forward never stores that tensor: the activation of a layer fused with its max pool (only the pooled tensor is
+        written), the image layer's raw output when its consumers recompute it.  ``buffer`` is a view of the root buffer starting at the
+        tensor's first channel: ``rows`` pixels of ``c`` values every ``ld`` elements (lanes c .. ld-1 are padding or a concat neighbour)."""
+        assert self.training, 'the summaries describe a training step'
+        skipped = set()
+        for op in self.graph.ops:
+            if op['kind'] == 'conv' and op['bn']:
+                if op['out'] in self.fused_pool:
+                    skipped.add(op['out'])
+                if self._first_fused(op):
+                    skipped.add(op['y'])
+        out = []
+        for t in self.graph.tensors:
+            if t.flat_of is not None:
+                continue                     # the same bytes as the tensor it re-reads
+            if t in skipped:
+                out.append((t, None))
+            else:
+                buf, ld = self.act[t]
+                out.append((t, (buf, self.B * t.h * t.w, t.c, ld)))
+        return out

@@ -623,3 +623,54 @@ def anchor_update(centroids, job_k, jobs, kmax, ws, n, done=None, iterations=Non
     score pass (centroids stay).  Either writes ``counts`` / ``avg_iou`` when given and clears the workspace; asynchronous."""
     call('yolo2_anchor_update', ptr(centroids), ptr(job_k), jobs, kmax, ptr(ws), 0 if ws is None else ws.numel() * ws.element_size(), n,
          ptr(done), ptr(iterations), ptr(counts), ptr(avg_iou), _stream())
+
+
+HIST_BUCKETS = 1550        # YOLO2_HIST_BUCKETS / YOLO2_HIST_WORDS of include/yolo2_hip.h
+HIST_WORDS = HIST_BUCKETS + 6
+
+
+class HistogramJobs(object):
+    """Device job table of yolo2_histogram, built once for a fixed list of tensors, with its result and workspace buffers.
+
+    ``jobs``: [(tensor, rows, c, ld)] -- ``tensor`` a contiguous f32 / bf16 device tensor (a view is fine: its data_ptr() is the job's base) of
+    which the job reads ``rows`` rows of ``c`` values with row stride ``ld``; (t, 1, n, n) is a flat range, rows = 0 an empty job.  The
+    extents are checked against the tensors here, so the kernel never reads past one.  The tensors are kept alive by this object."""
+
+    def __init__(self, jobs, device=None):
+        from ._lib import HistJob
+        assert len(jobs) > 0
+        self.tensors = [j[0] for j in jobs]
+        self.shapes = [(int(j[1]), int(j[2]), int(j[3])) for j in jobs]
+        self.device = device if device is not None else self.tensors[0].device
+        arr = (HistJob * len(jobs))()
+        first = 0
+        for d, (t, rows, c, ld) in zip(arr, jobs):
+            rows, c, ld = int(rows), int(c), int(ld)
+            assert t.is_cuda and t.is_contiguous() and 0 <= c <= ld and rows >= 0, (rows, c, ld)
+            extent = (rows - 1) * ld + c if rows > 0 and c > 0 else 0
+            assert extent <= t.numel(), 'histogram job of %d elements on a tensor of %d' % (extent, t.numel())
+            if extent == 0:
+                rows, c, ld = 0, 0, 0
+            d.base, d.rows, d.c, d.ld, d.dtype, d.first_item = (t.data_ptr() if extent else None), rows, c, ld, dtype_code(t.dtype), first
+            first += int(_lib.query('yolo2_histogram_items', rows, c, ld, d.dtype))
+        self.n, self.items = len(jobs), first
+        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
+        self.out = torch.zeros(self.n, HIST_WORDS, dtype=torch.int64, device=self.device)
+        self.ws = torch.empty(max(workspace_bytes('histogram', self.n) // 8, 1), dtype=torch.int64, device=self.device)
+
+    def launch(self):
+        """Enqueues the call on the current stream (no synchronisation); the records are in ``self.out`` [n][HIST_WORDS] once it has run."""
+        call('yolo2_histogram', ptr(self.table), self.n, self.items, ptr(self.out), self.out.numel() * 8, ptr(self.ws), self.ws.numel() * 8, _stream())
+        return self.out
+
+
+def decode_histograms(words):
+    """Host view of yolo2_histogram's records: ``words`` an int64 array [n][HIST_WORDS] (numpy).  -> list of dicts with counts (int64 [1550]),
+    min, max, sum, sum_squares (float), num, nonfinite (int)."""
+    words = np.ascontiguousarray(words).reshape(-1, HIST_WORDS)
+    out = []
+    for w in words:
+        stats = w[HIST_BUCKETS:HIST_BUCKETS + 4].view(np.float64)
+        out.append({'counts': w[:HIST_BUCKETS], 'min': float(stats[0]), 'max': float(stats[1]), 'sum': float(stats[2]), 'sum_squares': float(stats[3]),
+                    'num': int(w[HIST_BUCKETS + 4]), 'nonfinite': int(w[HIST_BUCKETS + 5])})
+    return out

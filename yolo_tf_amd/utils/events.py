@@ -7,10 +7,11 @@ and summarises the scalars its ``[summary] scalar`` pattern selects (config.ini:
 messages it needs:
 
     Event   { double wall_time = 1; int64 step = 2; oneof { string file_version = 3; Summary summary = 5; } }
-    Summary { repeated Value value = 1; }      Value { string tag = 1; float simple_value = 2; }
+    Summary { repeated Value value = 1; }      Value { string tag = 1; float simple_value = 2; HistogramProto histo = 5; }
+    HistogramProto { double min = 1, max = 2, num = 3, sum = 4, sum_squares = 5; repeated double bucket_limit = 6 [packed], bucket = 7 [packed]; }
 
-TensorBoard reads it like any ``events.out.tfevents.*`` file.  Image and histogram summaries of the reference (train.py:44-60)
-are not produced.  Host-side I/O only."""
+TensorBoard reads it like any ``events.out.tfevents.*`` file.  Histogram summaries (train.py:56-61 of the reference, ``[summary] histogram``
+and ``gradients``) come from yolo_tf_amd/summary.py; image summaries (train.py:44-53) are not produced.  Host-side I/O only."""
 import os
 import socket
 import struct
@@ -39,16 +40,57 @@ def _ld(field, payload):          # length-delimited field
     return _varint((field << 3) | 2) + _varint(len(payload)) + payload
 
 
-def encode_event(wall_time, step=None, file_version=None, scalars=None):
+def encode_histogram(h):
+    """HistogramProto bytes of ``h``: a dict with min, max, num, sum, sum_squares and the already collapsed bucket_limit / bucket lists
+    (summary.encode_buckets).  proto3 rules: a scalar field equal to zero is not written; the repeated doubles are packed."""
+    out = b''
+    for field, key in ((1, 'min'), (2, 'max'), (3, 'num'), (4, 'sum'), (5, 'sum_squares')):
+        bits = struct.pack('<d', float(h[key]))
+        if bits != b'\0' * 8:
+            out += _varint((field << 3) | 1) + bits
+    for field, key in ((6, 'bucket_limit'), (7, 'bucket')):
+        if len(h[key]):
+            out += _ld(field, struct.pack('<%dd' % len(h[key]), *[float(v) for v in h[key]]))
+    return out
+
+
+def decode_histogram(buf):
+    out = {'min': 0.0, 'max': 0.0, 'num': 0.0, 'sum': 0.0, 'sum_squares': 0.0, 'bucket_limit': [], 'bucket': []}
+    keys = {1: 'min', 2: 'max', 3: 'num', 4: 'sum', 5: 'sum_squares', 6: 'bucket_limit', 7: 'bucket'}
+    i = 0
+    while i < len(buf):
+        key, i = _read_varint(buf, i)
+        f, wt = key >> 3, key & 7
+        if wt == 1:
+            v, i = struct.unpack('<d', buf[i:i + 8])[0], i + 8
+            if f in (6, 7):
+                out[keys[f]].append(v)         # (an unpacked repeated double: legal on the wire)
+            elif f in keys:
+                out[keys[f]] = v
+        elif wt == 2:
+            n, i = _read_varint(buf, i)
+            if f in (6, 7):
+                out[keys[f]] += list(struct.unpack('<%dd' % (n // 8), buf[i:i + n]))
+            i += n
+        else:
+            raise ValueError('wire type %d in a HistogramProto' % wt)
+    return out
+
+
+def encode_event(wall_time, step=None, file_version=None, scalars=None, histograms=None):
+    """``histograms``: [(tag, dict for encode_histogram)], written after the scalars into the same Summary; None (or empty with no scalars)
+    leaves the bytes of a scalar-only event exactly as they were."""
     ev = _varint((1 << 3) | 1) + struct.pack('<d', float(wall_time))
     if step is not None and step != 0:
         ev += _varint((2 << 3) | 0) + _varint(int(step))
     if file_version is not None:
         ev += _ld(3, file_version.encode())
-    if scalars is not None:
+    if scalars is not None or histograms:
         summary = b''
-        for tag, value in scalars:
+        for tag, value in (scalars or ()):
             summary += _ld(1, _ld(1, tag.encode()) + _varint((2 << 3) | 5) + struct.pack('<f', float(value)))
+        for tag, h in (histograms or ()):
+            summary += _ld(1, _ld(1, tag.encode()) + _ld(5, encode_histogram(h)))
         ev += _ld(5, summary)
     return ev
 
@@ -73,7 +115,7 @@ def decode_event(buf):
                 raise ValueError('wire type %d' % wt)
             yield f, wt, v
 
-    out = {'step': 0, 'scalars': []}
+    out = {'step': 0, 'scalars': [], 'histograms': []}
     for f, wt, v in fields(buf):
         if f == 1:
             out['wall_time'] = struct.unpack('<d', v)[0]
@@ -84,13 +126,18 @@ def decode_event(buf):
         elif f == 5:
             for f2, _, val in fields(v):
                 if f2 == 1:
-                    tag, simple = None, None
+                    tag, simple, histo = None, None, None
                     for f3, _, x in fields(val):
                         if f3 == 1:
                             tag = x.decode()
                         elif f3 == 2:
                             simple = struct.unpack('<f', x)[0]
-                    out['scalars'].append((tag, simple))
+                        elif f3 == 5:
+                            histo = decode_histogram(x)
+                    if histo is not None:
+                        out['histograms'].append((tag, histo))
+                    else:
+                        out['scalars'].append((tag, simple))
     return out
 
 
@@ -123,6 +170,10 @@ class FileWriter(object):
         """values: {tag: float} or [(tag, float)]."""
         items = list(values.items()) if isinstance(values, dict) else list(values)
         self._write(encode_event(time.time() if wall_time is None else wall_time, step=step, scalars=items))
+
+    def add_histograms(self, step, histograms, scalars=None, wall_time=None):
+        """histograms: [(tag, dict for encode_histogram)]; ``scalars`` (optional [(tag, float)]) go into the same event."""
+        self._write(encode_event(time.time() if wall_time is None else wall_time, step=step, scalars=scalars, histograms=list(histograms)))
 
     def add_training_summary(self, step, fetched):
         """The five scalars of the reference's [summary] section from TrainSession.fetch()'s dict."""
