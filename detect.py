@@ -84,9 +84,13 @@ def main():
     builder = yolo.Builder(args, config)
     builder(None)
     dtype = args.dtype or (config.get('mi355x', 'dtype') if config.has_option('mi355x', 'dtype') else 'bf16')
-    sess = DetectSession(builder, 1, dtype=dtype)
     from yolo_tf_amd import tf_checkpoint
     logdir = utils.get_logdir(config)
+    calibration = None
+    if dtype == 'int8':       # post-training quantised inference: the scales quantize.py measured for this checkpoint
+        from yolo_tf_amd import quant
+        calibration = quant.calibration_path(logdir, args.calibration)
+    sess = DetectSession(builder, 1, dtype=dtype, calibration=calibration)
     model_path = checkpoint.latest_checkpoint(logdir)
     tf_path = None if model_path else tf_checkpoint.latest_checkpoint(logdir)      # a logdir the reference trained (tf.train.latest_checkpoint, detect.py:104)
     if model_path is None and tf_path is None:
@@ -117,7 +121,8 @@ def make_args():
     parser.add_argument('-e', '--exts', nargs='+', default=['.jpg', '.png'])
     parser.add_argument('--level', default='info', help='logging level')
     parser.add_argument('--output', help='directory for annotated images (the reference opens a matplotlib window instead)')
-    parser.add_argument('--dtype', default=None, choices=['bf16', 'f32'])
+    parser.add_argument('--dtype', default=None, choices=['bf16', 'f32', 'int8'], help="'int8': post-training quantised inference (needs a calibration)")
+    parser.add_argument('--calibration', default=None, help='--dtype int8: the file quantize.py wrote (default: calibration.npz in the logdir)')
     return parser.parse_args()
 
 

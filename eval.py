@@ -51,8 +51,12 @@ def main():
     builder = yolo.Builder(args, config)
     builder(None)
     dtype = args.dtype or (config.get('mi355x', 'dtype') if config.has_option('mi355x', 'dtype') else 'bf16')
-    sess = DetectSession(builder, args.batch_size, dtype=dtype)
     logdir = utils.get_logdir(config)
+    calibration = None
+    if dtype == 'int8':       # post-training quantised inference: the scales quantize.py measured for this checkpoint
+        from yolo_tf_amd import quant
+        calibration = quant.calibration_path(logdir, args.calibration)
+    sess = DetectSession(builder, args.batch_size, dtype=dtype, calibration=calibration)
     model_path = checkpoint.latest_checkpoint(logdir)
     tf_path = None if model_path else tf_checkpoint.latest_checkpoint(logdir)
     if model_path is None and tf_path is None:
@@ -66,7 +70,7 @@ def main():
                              crowd=crowd, area=area)
     result = evaluate.evaluate(builder, sess, data, mode=args.mode, threshold=args.threshold, threshold_iou=args.threshold_iou, iou=args.iou,
                                preprocess_mode=PREPROCESS[args.preprocess], max_records=args.max_records, protocol=args.protocol)
-    extra = dict(names=list(builder.names), images=len(images), checkpoint=model_path or tf_path, global_step=int(step),
+    extra = dict(names=list(builder.names), images=len(images), checkpoint=model_path or tf_path, global_step=int(step), calibration=calibration,
                  config={k: getattr(args, k) for k in ('config', 'profile', 'data', 'batch_size', 'threshold', 'threshold_iou', 'iou', 'mode', 'protocol',
                                                        'preprocess', 'dtype', 'limit', 'images', 'seed')})
     if args.protocol == 'coco':
@@ -111,7 +115,8 @@ def make_args(argv=None):
     parser.add_argument('--images', type=int, default=32, help='--data synthetic: number of images')
     parser.add_argument('--seed', type=int, default=0, help='--data synthetic: seed')
     parser.add_argument('--max_records', type=int, default=None, help='capacity of the record buffer (default: the worst case of the mode)')
-    parser.add_argument('--dtype', default=None, choices=['bf16', 'f32'])
+    parser.add_argument('--dtype', default=None, choices=['bf16', 'f32', 'int8'], help="'int8': post-training quantised inference (needs a calibration)")
+    parser.add_argument('--calibration', default=None, help='--dtype int8: the file quantize.py wrote (default: calibration.npz in the logdir)')
     parser.add_argument('--level', default='info', help='logging level')
     return parser.parse_args(argv)
 

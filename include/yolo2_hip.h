@@ -733,6 +733,42 @@ size_t yolo2_histogram_result_bytes(int njobs);                    /* njobs * YO
 int yolo2_histogram_items(long long rows, int c, int ld, int dtype);   /* work items of one job (a count, not a status); 0 for an empty or malformed one */
 int yolo2_histogram(const yolo2_hist_job *jobs, int njobs, int items, void *out, size_t out_bytes, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- int8 inference (post-training quantisation; DESIGN.md section 15, specification: tests/quant_ref.py) -----------------------------
+ * Symmetric int8 in -127 .. 127: q = clip(rint(x * inv_s), -127, 127) in f32, NaN -> 0, inv_s = float32(1) / s computed by the host.
+ *
+ * yolo2_conv2d_i8: NHWC implicit GEMM on the int8 MFMA, 3x3 / 1x1, stride 1, SAME; arguments as yolo2_conv2d_bias_leaky with byte operands:
+ *   acc[m, n] = sum over taps and channels of P * F, exact int32 (F: [Nf][ksize*ksize][Cp] int8, the kernel's own layout, made by the host)
+ *   t = float(acc) * mult[n];  y = t + bias[n];  y = y > 0 ? y : y * alpha     -- f32, every operation rounded (no fma); alpha == 1: linear
+ *   out_kind YOLO2_I8_OUT_I8:   O int8  = clip(rint(y * inv_s_out), -127, 127)
+ *            YOLO2_I8_OUT_BF16: O bf16  = y rounded to nearest even (the logits yolo2_head_decode reads)
+ *            YOLO2_I8_OUT_F32:  O f32   = y
+ *            YOLO2_I8_OUT_ACC:  O int32 = acc, the raw accumulators (diagnostic mode of the tests; mult / bias may be NULL)
+ * ldp / ldo: pixel strides in ELEMENTS of P / O, so a producer can write at a channel offset inside a concat buffer.  Nf is arbitrary (the
+ * store tail is masked).  Cp and ldp must be multiples of 16 and P, F 16-byte aligned; anything else is YOLO2_E_ARG ("argument check
+ * failed") before any launch.  No workspace, no library-owned state; ksize * ksize * Cp < 2^17 keeps every int32 sum exact. */
+enum { YOLO2_I8_OUT_I8 = 0, YOLO2_I8_OUT_BF16 = 1, YOLO2_I8_OUT_F32 = 2, YOLO2_I8_OUT_ACC = 3 };
+int yolo2_conv2d_i8(const void *P, const void *F, const float *mult, const float *bias, void *O, int B, int H, int W, int Cp, int ldp,
+                    int Nf, int ldo, int ksize, float alpha, float inv_s_out, int out_kind, void *stream);
+/* Running abs-max of a list of tensors in one launch (calibration).  jobs: DEVICE table; job j reads `rows` rows of `c` values (dtype
+ * YOLO2_F32 / YOLO2_BF16) with row stride `ld` and folds into record `slot` of out: out[2*slot] = max(out[2*slot], bit pattern of the
+ * largest finite |x|), out[2*slot + 1] += number of non-finite values (ignored by the maximum).  Several jobs may share a slot.  The caller
+ * zeroes `out` once; successive calls (batches) keep accumulating.  Non-negative floats order like their bit patterns, so the maximum is an
+ * integer atomic and the result is exact and order-independent. */
+typedef struct yolo2_absmax_job {
+    const void *base;
+    long long rows;
+    int c, ld, dtype;
+    int slot;
+} yolo2_absmax_job;
+int yolo2_absmax(const yolo2_absmax_job *jobs, int njobs, unsigned *out, void *stream);
+/* Q[r*ldq + j] = quantise(X[r*ldx + j]) for r < rows, j < c (X: f32 / bf16) */
+int yolo2_quantize(const void *X, int ldx, void *Q, int ldq, long rows, int c, float inv_s, int dtype, void *stream);
+/* 2x2 SAME max pool on int8 bytes, stride 2 (output ceil(H/2) x ceil(W/2)) or stride 1 (output H x W); the window is clipped at the
+ * bottom / right edge.  lda / ldp: pixel strides of A / P. */
+int yolo2_maxpool_i8(const void *A, int lda, void *P, int ldp, int B, int H, int W, int C, int stride, void *stream);
+/* yolo2_reorg on int8 bytes: out[b,y,x,(sy*2+sx)*C+c] = in[b,2y+sy,2x+sx,c]; `in` dense, `out` with pixel stride ldo */
+int yolo2_reorg_i8(const void *in, void *out, int B, int H, int W, int C, int ldo, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

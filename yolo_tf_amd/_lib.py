@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('YOLO2_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libyolo2hip.so')     # the override is for timing-ablation builds (scripts/abl_build.sh)
 
 F32, BF16 = 0, 1
+I8_OUT_I8, I8_OUT_BF16, I8_OUT_F32, I8_OUT_ACC = 0, 1, 2, 3      # out_kind of yolo2_conv2d_i8
 
 
 class HipKernelError(RuntimeError):
@@ -109,6 +110,11 @@ SIGNATURES = {
     'yolo2_anchor_assign': [_p, _i, _p, _p, _i, _i, _p, ctypes.c_size_t, _p, _p, _p],
     'yolo2_anchor_update': [_p, _p, _i, _i, _p, ctypes.c_size_t, _i, _p, _p, _p, _p, _p],
     'yolo2_histogram': [_p, _i, _i, _p, ctypes.c_size_t, _p, ctypes.c_size_t, _p],
+    'yolo2_conv2d_i8': [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, _p],
+    'yolo2_absmax': [_p, _i, _p, _p],
+    'yolo2_quantize': [_p, _i, _p, _i, _l, _i, _f, _i, _p],
+    'yolo2_maxpool_i8': [_p, _i, _p, _i, _i, _i, _i, _i, _i, _p],
+    'yolo2_reorg_i8': [_p, _p, _i, _i, _i, _i, _i, _p],
 }
 
 # host queries / diagnostics: (restype, argtypes); bound in load() next to the status-returning entries above
@@ -169,6 +175,11 @@ class AugmentParams(ctypes.Structure):
 class HistJob(ctypes.Structure):
     """yolo2_hist_job of include/yolo2_hip.h"""
     _fields_ = [('base', ctypes.c_void_p), ('rows', ctypes.c_longlong), ('c', _i), ('ld', _i), ('dtype', _i), ('first_item', _i)]
+
+
+class AbsmaxJob(ctypes.Structure):
+    """yolo2_absmax_job of include/yolo2_hip.h"""
+    _fields_ = [('base', ctypes.c_void_p), ('rows', ctypes.c_longlong), ('c', _i), ('ld', _i), ('dtype', _i), ('slot', _i)]
 
 
 class FilterDesc(ctypes.Structure):

@@ -674,3 +674,55 @@ def decode_histograms(words):
         out.append({'counts': w[:HIST_BUCKETS], 'min': float(stats[0]), 'max': float(stats[1]), 'sum': float(stats[2]), 'sum_squares': float(stats[3]),
                     'num': int(w[HIST_BUCKETS + 4]), 'nonfinite': int(w[HIST_BUCKETS + 5])})
     return out
+
+
+# ---- int8 inference (include/yolo2_hip.h "int8 inference"; specification: tests/quant_ref.py) ----------------------------------------
+
+I8_OUT_I8, I8_OUT_BF16, I8_OUT_F32, I8_OUT_ACC = _lib.I8_OUT_I8, _lib.I8_OUT_BF16, _lib.I8_OUT_F32, _lib.I8_OUT_ACC
+
+
+def conv2d_i8(P, F, mult, bias, O, B, H, W, Cp, ldp, Nf, ldo, ksize, alpha, inv_s_out, out_kind):
+    """yolo2_conv2d_i8: int8 P / F, int32 accumulation, epilogue t = acc*mult, y = t + bias, leaky (alpha == 1: linear), then ``out_kind``:
+    int8 clip(rint(y * inv_s_out)), bf16, f32, or the raw int32 accumulators (I8_OUT_ACC: mult / bias may be None)."""
+    call('yolo2_conv2d_i8', ptr(P), ptr(F), ptr(mult), ptr(bias), ptr(O), B, H, W, Cp, ldp, Nf, ldo, ksize, float(alpha), float(inv_s_out), out_kind, _stream())
+
+
+class AbsmaxJobs(object):
+    """Device job table of yolo2_absmax over a fixed list of tensors, with its running result.
+
+    ``jobs``: [(tensor, rows, c, ld, slot)] -- as HistogramJobs, plus the record the job folds into (several jobs may share one).  ``launch()``
+    folds the tensors' current contents into the running records; ``result()`` -> (abs-max f32 [nslots], non-finite counts int64 [nslots])."""
+
+    def __init__(self, jobs, nslots, device=None):
+        from ._lib import AbsmaxJob
+        assert len(jobs) > 0
+        self.tensors = [j[0] for j in jobs]
+        self.device = device if device is not None else self.tensors[0].device
+        arr = (AbsmaxJob * len(jobs))()
+        for d, (t, rows, c, ld, slot) in zip(arr, jobs):
+            rows, c, ld, slot = int(rows), int(c), int(ld), int(slot)
+            assert t.is_cuda and t.is_contiguous() and 0 < c <= ld and rows > 0 and 0 <= slot < nslots, (rows, c, ld, slot)
+            assert (rows - 1) * ld + c <= t.numel(), 'abs-max job of %d elements on a tensor of %d' % ((rows - 1) * ld + c, t.numel())
+            d.base, d.rows, d.c, d.ld, d.dtype, d.slot = t.data_ptr(), rows, c, ld, dtype_code(t.dtype), slot
+        self.n, self.nslots = len(jobs), int(nslots)
+        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
+        self.out = torch.zeros(self.nslots, 2, dtype=torch.int32, device=self.device)
+
+    def launch(self):
+        call('yolo2_absmax', ptr(self.table), self.n, ptr(self.out), _stream())
+
+    def result(self):
+        words = self.out.cpu().numpy().view(np.uint32)
+        return np.ascontiguousarray(words[:, 0]).view(np.float32).copy(), words[:, 1].astype(np.int64)
+
+
+def quantize(X, ldx, Q, ldq, rows, c, inv_s):
+    call('yolo2_quantize', ptr(X), ldx, ptr(Q), ldq, rows, c, float(inv_s), dtype_code(X.dtype), _stream())
+
+
+def maxpool_i8(A, lda, P, ldp, B, H, W, C, stride):
+    call('yolo2_maxpool_i8', ptr(A), lda, ptr(P), ldp, B, H, W, C, stride, _stream())
+
+
+def reorg_i8(x, out, B, H, W, C, ldo):
+    call('yolo2_reorg_i8', ptr(x), ptr(out), B, H, W, C, ldo, _stream())

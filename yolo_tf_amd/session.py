@@ -292,13 +292,25 @@ class TrainSession(object):
 class DetectSession(object):
     """Forward with moving-average BN + decode + batched on-GPU NMS (detect.py:69-80)."""
 
-    def __init__(self, builder, batch_size=1, dtype='bf16', seed=0):
+    def __init__(self, builder, batch_size=1, dtype='bf16', seed=0, calibration=None):
         assert not builder.training
         self.builder = builder
         self.model = m = builder.model
-        self.engine = Engine(builder.graph, batch_size, dtype, training=False, seed=seed)
-        dev = self.engine.device
         self.v1 = getattr(builder, 'family', 'yolo2') == 'yolo'
+        if dtype == 'int8':
+            # post-training quantised inference (yolo_tf_amd/quant.py): int8 activations and filters, bf16 logits -- decode, NMS and the
+            # evaluators below read those and do not change
+            from .quant import Calibration, QuantEngine
+            if self.v1:
+                raise NotImplementedError("dtype='int8' covers the YOLOv2 family: the YOLO (v1) fully connected head is not quantised")
+            if calibration is None:
+                raise ValueError("dtype='int8' needs a calibration (quantize.py writes one; yolo_tf_amd.quant.calibrate makes one)")
+            if not isinstance(calibration, Calibration):
+                calibration = Calibration.load(calibration)
+            self.engine = QuantEngine(builder.graph, batch_size, calibration, seed=seed)
+        else:
+            self.engine = Engine(builder.graph, batch_size, dtype, training=False, seed=seed)
+        dev = self.engine.device
         self.B, self.A, self.C = batch_size, (m.boxes_per_cell if self.v1 else len(m.anchors)), m.classes
         n = m.cells * self.A
         self.N = n
