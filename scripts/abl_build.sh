@@ -5,8 +5,8 @@
 # usage: scripts/abl_build.sh 1 2 4 8 16 ...   (bit masks, Y2_ABL)
 # Links the product's other objects: run yolo_tf_amd/csrc/build.py first.
 cd "$(dirname "$0")/.."; S=yolo_tf_amd/csrc; O=scripts/experiments/build; mkdir -p $O
-# the copy and every header it includes
-cp $S/conv_igemm.hip $S/common.h $S/conv_shared.h $S/conv_epilogue.h $O/ && sed -i 's|"../../include/yolo2_hip.h"|"../../../include/yolo2_hip.h"|' $O/common.h
+# the copy and every header of the directory
+cp $S/conv_igemm.hip $S/*.h $O/ && sed -i 's|"../../include/yolo2_hip.h"|"../../../include/yolo2_hip.h"|' $O/common.h
 patch -s $O/conv_igemm.hip scripts/experiments/conv_igemm_ablation_hooks.patch || { echo "the ablation patch no longer applies: re-cut it"; exit 1; }
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unused-result"
 for b in "$@"; do
@@ -14,6 +14,7 @@ for b in "$@"; do
 done
 wait
 for b in "$@"; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $O/libabl_$b.so $O/conv_igemm_$b.o $(ls $S/*.o | grep -v -e '/conv_igemm\.o$' -e '_exp\.o$') || exit 1
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $O/libabl_$b.so $O/conv_igemm_$b.o $(python $S/build.py --objects | grep -v '/conv_igemm\.o$') || exit 1
+  python scripts/check_lib_symbols.py $O/libabl_$b.so || exit 1
 done
 ls -la $O/*.so

@@ -13,17 +13,20 @@ cd "$(dirname "$0")/../yolo_tf_amd/csrc" || exit 1
 python build.py > /dev/null || exit 1          # the product objects, up to date
 WHAT="${*:-pp w3 c32 s4}"
 HIPCC="/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unused-result"
-PP=conv_pp.o; W3=conv_wgrad3.o; C32=conv_c32.o; S4=conv_s4.o; D1=conv_d1.o; W32=conv_wgrad_c32.o
+OBJS=$(python build.py --objects) || exit 1        # the product's one list of objects; an experiment object replaces its product twin
 for w in $WHAT; do
   case $w in
-    pp)  $HIPCC -DY2P_EXPERIMENTS -c conv_pp.hip -o conv_pp_exp.o || exit 1; PP=conv_pp_exp.o ;;
-    w3)  $HIPCC -DY2W3_EXPERIMENTS -c conv_wgrad3.hip -o conv_wgrad3_exp.o || exit 1; W3=conv_wgrad3_exp.o ;;
-    c32) $HIPCC -DY2C32_EXPERIMENTS -c conv_c32.hip -o conv_c32_exp.o || exit 1; C32=conv_c32_exp.o ;;
-    s4)  $HIPCC -DY2S_EXPERIMENTS -c conv_s4.hip -o conv_s4_exp.o || exit 1; S4=conv_s4_exp.o ;;
-    w32) $HIPCC -DY2W32_EXPERIMENTS -c conv_wgrad_c32.hip -o conv_wgrad_c32_exp.o || exit 1; W32=conv_wgrad_c32_exp.o ;;
-    d1)  $HIPCC -DY2D1_EXPERIMENTS -c conv_d1.hip -o conv_d1_exp.o || exit 1; D1=conv_d1_exp.o ;;
+    pp)  U=conv_pp;        D=Y2P_EXPERIMENTS ;;
+    w3)  U=conv_wgrad3;    D=Y2W3_EXPERIMENTS ;;
+    c32) U=conv_c32;       D=Y2C32_EXPERIMENTS ;;
+    s4)  U=conv_s4;        D=Y2S_EXPERIMENTS ;;
+    w32) U=conv_wgrad_c32; D=Y2W32_EXPERIMENTS ;;
+    d1)  U=conv_d1;        D=Y2D1_EXPERIMENTS ;;
     *) echo "unknown kernel '$w' (pp, w3, w32, c32, s4, d1)"; exit 1 ;;
   esac
+  $HIPCC -D$D -c $U.hip -o ${U}_exp.o || exit 1
+  OBJS=$(echo "$OBJS" | sed "s|/$U\\.o\$|/${U}_exp.o|")
 done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o libyolo2hip_exp.so conv_igemm.o $PP $S4 conv_wgrad.o $W3 $W32 $C32 conv_c64.o $D1 conv_first.o elementwise.o head.o yolo1.o nms.o augment.o || exit 1
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o libyolo2hip_exp.so $OBJS || exit 1
+python ../../scripts/check_lib_symbols.py libyolo2hip_exp.so || exit 1
 ls -la libyolo2hip_exp.so

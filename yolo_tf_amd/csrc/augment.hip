@@ -196,6 +196,8 @@ __global__ __launch_bounds__(256) void augment_apply_kernel(const unsigned char 
     }
 }
 
+// bytes of the caller-owned scratch `ws` below: three doubles per image
+extern "C" size_t yolo2_augment_workspace_bytes(int B) { return (size_t)3 * (size_t)(B > 0 ? B : 0) * sizeof(double); }
 extern "C" int yolo2_augment_images(const unsigned char *src, const yolo2_augment_params *params_device, double *ws, float *out, int B, int H,
                                     int W, int any_contrast, void *stream) {
     Y2_CHECK_ARG(src && params_device && out && B > 0 && H > 0 && W > 0);

@@ -19,7 +19,12 @@ SOURCES = {
     'conv_c64.hip': [],
     'conv_d1.hip': [],
     'conv_first.hip': [],
-    'elementwise.hip': [],
+    'runtime.hip': [],
+    'filter_prep.hip': [],
+    'bn_stats.hip': [],
+    'bn.hip': [],
+    'layout.hip': [],
+    'optim.hip': [],
     'head.hip': ['-ffp-contract=off'],
     'yolo1.hip': ['-ffp-contract=off'],
     'nms.hip': ['-ffp-contract=off'],
@@ -44,17 +49,27 @@ def _stale(out, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def objects():
+    """The product's object files, in link order: the ONE list (`python build.py --objects` prints it for the experiment build scripts)."""
+    return [os.path.join(HERE, src.replace('.hip', '.o')) for src in SOURCES]
+
+
 def build(force=False, verbose=True):
     hipcc = os.environ.get('HIPCC', os.path.join(ROCM, 'bin', 'hipcc'))
     # every header of this directory: editing any of them rebuilds
     headers = sorted(os.path.join(HERE, h) for h in os.listdir(HERE) if h.endswith('.h')) + [os.path.join(HERE, '..', '..', 'include', 'yolo2_hip.h'), os.path.abspath(__file__)]
-    objs, cmds = [], []
-    for src, extra in SOURCES.items():
+    objs, cmds = objects(), []
+    for (src, extra), o in zip(SOURCES.items(), objs):
         s = os.path.join(HERE, src)
-        o = os.path.join(HERE, src.replace('.hip', '.o'))
         if force or _stale(o, [s] + headers):
             cmds.append([hipcc] + COMMON + extra + ['-c', s, '-o', o])
-        objs.append(o)
+    # an object of a source that left SOURCES (a renamed or split unit) must not linger for anything that globs the directory; the
+    # experiment builds' own *_exp.o are theirs
+    for f in os.listdir(HERE):
+        if f.endswith('.o') and not f.endswith('_exp.o') and os.path.join(HERE, f) not in objs:
+            os.remove(os.path.join(HERE, f))
+            if verbose:
+                print('removed stale object %s' % f, flush=True)
     if cmds:      # independent translation units: compile them side by side (YOLO2_BUILD_JOBS, default: the CPUs of this host, at most 8)
         from concurrent.futures import ThreadPoolExecutor
         jobs = max(1, min(int(os.environ.get('YOLO2_BUILD_JOBS', min(8, os.cpu_count() or 1))), len(cmds)))
@@ -100,4 +115,7 @@ def build_comm(force=False, verbose=True):
 
 
 if __name__ == '__main__':
-    build(force='--force' in sys.argv)
+    if '--objects' in sys.argv:
+        print('\n'.join(objects()))
+    else:
+        build(force='--force' in sys.argv)

@@ -114,7 +114,7 @@ int y2_first_layer_fwd(const void *P, const void *F, void *O, int B, int H, int 
 int y2_first_layer_wgrad(const void *X, const void *dY, float *dW, int B, int H, int W, int Cin, int dtype, hipStream_t st, float *ws = nullptr);      // ws: one slot per workgroup
 int y2_first_layer_wgrad_blocks(int B, int H, int W);
 
-// batch-norm partial sums produced by the convolution epilogue: [2][Y2_BN_PART_ROWS][C] f32 (elementwise.hip finalises)
+// batch-norm partial sums produced by the convolution epilogue: [2][Y2_BN_PART_ROWS][C] f32 (bn_stats.hip / the *_fin consumers of bn.hip finalise)
 #define Y2_BN_PART_ROWS YOLO2_BN_PART_ROWS
 // the 2 x Y2_BN_PART_ROWS partial rows of a fused BN-backward data gradient -> dgamma (plane 0), dbeta (plane 1); rows zeroed again
 int y2_bn_part_to_grads(float *part, int C, float *dgamma, float *dbeta, hipStream_t st);
@@ -150,6 +150,12 @@ __host__ __device__ static inline long y2_filter_koff(int tap, int c, int ld, in
 }
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+static inline int ew_grid(long total) {      // 256-thread workgroups of a grid-stride elementwise kernel
+    long g = (total + 255) / 256;
+    if (g > 8192) g = 8192;
+    if (g < 1) g = 1;
+    return (int)g;
+}
 // The library's A/B switches are integers read once from the environment; unset = the measured default.
 static inline int y2_env_int(const char *name, int dflt) {
     const char *e = getenv(name);

@@ -5,6 +5,7 @@
 // are issued, how far the loops are unrolled and where the waits sit is scheduling and stays with each kernel.
 #pragma once
 #include "conv_shared.h"
+#include "bn_leaky.h"
 
 // ---- partial rows.  The rows are indexed by a row id the kernel derives from its plan (conv_shared.h: Y2IgemmPlan, Y2P_ / Y2S_ / D1_STAT_ROWS*);
 // the host counts the same ids and, when they exceed the rows the consumer reads, wraps them (Y2BnBwd::stat_mask_inv).  When they fit,
@@ -50,14 +51,14 @@ template <typename T> struct Y2BnBwdLane {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 cmu[k + q] = a[q];
-                cinv[k + q] = 1.0f / sqrtf(b[q] + bz.eps);
+                cinv[k + q] = bn_inv_std(b[q], bz.eps);
                 cga[k + q] = c[q];
                 cbt[k + q] = d[q];
                 ps[0][k + q] = ps[1][k + q] = 0.f;
             }
         }
     }
-    // same arithmetic as bn_bwd_reduce_kernel (elementwise.hip), on the rounded gradient d just stored and the producer's stored y
+    // bn_leaky.h bn_leaky_bwd, spelled out (the helper perturbs these MFMA kernels' schedules), on the rounded gradient d just stored and the producer's stored y
     __device__ __forceinline__ void add(const Y2BnBwd &bz, const Vec16<T> &y, const Vec16<T> &d) {
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {

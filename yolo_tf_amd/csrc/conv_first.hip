@@ -16,6 +16,7 @@
 //     keeps 3 accumulator tiles over all its segments, waves are combined through LDS and written with one
 //     f32 atomic per output element per workgroup.
 #include "common.h"
+#include "bn_leaky.h"
 #include <type_traits>
 
 #define Y2_OOB 0x80000000u
@@ -23,9 +24,6 @@
 // ---------------------------------------------------------------------------------------------------
 // shared staging: halo rows h-1, h, h+1, pixels w0-1 .. w0+32 of image b, 8 channels per pixel
 // ---------------------------------------------------------------------------------------------------
-template <int N> struct IdxPackFirst;                     // N arg-max code bytes as one integer
-template <> struct IdxPackFirst<8> { typedef unsigned long long type; };
-template <> struct IdxPackFirst<4> { typedef unsigned type; };
 template <typename T> struct First {
     static constexpr int PXB = 8 * sizeof(T);              // bytes per halo pixel (16 bf16 / 32 f32)
     static constexpr int HPIECES = PXB / 16;               // DMA pieces per halo row (64 lanes x 16 B = 1 KiB)
@@ -217,7 +215,7 @@ __global__ __launch_bounds__(256) void conv_first_pool_kernel(const T *__restric
         }
     }
     // this lane's channel constants (one filter per lane)
-    const float mu = bn.mean[n], inv = 1.0f / sqrtf(bn.var[n] + bn.eps), ga = bn.gamma[n], bt = bn.beta[n];
+    const float mu = bn.mean[n], inv = bn_inv_std(bn.var[n], bn.eps), ga = bn.gamma[n], bt = bn.beta[n];
     const float sc = inv * ga;
     const float invM = 1.0f / (float)((long)B * H * W);
     const float dgm = MODE == 2 ? bn.dgamma[n] * invM : 0.f, dbm = MODE == 2 ? bn.dbeta[n] * invM : 0.f;
@@ -278,6 +276,7 @@ __global__ __launch_bounds__(256) void conv_first_pool_kernel(const T *__restric
                 }
             }
         }
+        // the element arithmetic below is bn_leaky.h's (bn_leaky, pool_first_max, bn_leaky_bwd, bn_bwd_apply), spelled out: the helpers perturb this MFMA kernel's schedule
         // y as the unfused path stores it (rounded to T), window by window: registers r0, r0+1 of both rows = the 2x2 window of pooled
         // pixel p = 4q + 2*half + j of this segment
         const long prow = ((long)b * OH + h2) * OW + (w0 >> 1);       // first pooled pixel of the segment
@@ -512,7 +511,7 @@ __global__ __launch_bounds__(256, 3) void conv_first_wgrad_bn_kernel(const T *__
     const __amdgpu_buffer_rsrc_t rsrcX = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(X), 0, x_bytes, 0x00020000);
     const int SW = (W + 31) / 32, OH = H >> 1, OW = W >> 1;
     const int chunk = lane % CH;                             // 64 % CH == 0: a lane keeps its channel chunk in every iteration
-    typedef typename IdxPackFirst<N>::type pack_t;
+    typedef typename IdxPack<N>::type pack_t;
 
     // y, pooled gradient and arg-max codes of a segment go straight to registers, one segment ahead; only the halo and dy need LDS (8 KB per wave)
     struct Pre { Vec16<T> y[NIT], d[NIT]; pack_t p[NIT]; };
@@ -580,7 +579,8 @@ __global__ __launch_bounds__(256, 3) void conv_first_wgrad_bn_kernel(const T *__
         const f32x4 z = {0.f, 0.f, 0.f, 0.f};
         for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < zero_vec4; i += nthreads) reinterpret_cast<f32x4 *>(zero)[i] = z;
     }
-    // per-channel constants of this lane's chunk.  bn_bwd_apply_fin_kernel computes dy = (ga inv) (g - dbeta / M - xh dgamma / M) with xh = (y - mu) inv,
+    // per-channel constants of this lane's chunk, for a pre-multiplied form of bn_leaky.h's backward term (a different expression, not a copy of it).
+    // bn_bwd_apply_fin_kernel computes dy = (ga inv) (g - dbeta / M - xh dgamma / M) with xh = (y - mu) inv,
     // z = (y - mu)(inv ga) + bt, g = z >= 0 ? da : alpha da; here the same value as two multiply-adds on four constants per channel (32 registers instead
     // of 48 -- the difference between two and three waves per SIMD):  z = y A + o,  dy = da (z >= 0 ? A : alpha A) + (y Bc + Cc)
     const float invM = 1.0f / (float)((long)B * H * W);
@@ -588,7 +588,7 @@ __global__ __launch_bounds__(256, 3) void conv_first_wgrad_bn_kernel(const T *__
 #pragma unroll
     for (int j = 0; j < N; ++j) {
         const int c = chunk * N + j;
-        const float mu = mean[c], inv = 1.0f / sqrtf(var[c] + eps);
+        const float mu = mean[c], inv = bn_inv_std(var[c], eps);
         cA[j] = gamma[c] * inv;
         cAa[j] = alpha * cA[j];
         cO[j] = beta[c] - mu * cA[j];

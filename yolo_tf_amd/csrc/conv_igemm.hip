@@ -46,7 +46,7 @@
 //     time: 3.6x less fabric traffic on the 3072-channel layer (profiles/r03_l2_stationary_ab.md; the time moved 1.8 %: issue-bound).
 //   * Statistics rows: a producer leaves one partial row per (pixel tile, wave row) while that is no more than the consumer's
 //     prologue reads (y2_stat_rows_limit: 128 rows for >= 128 bf16 channels), else it wraps around 16-128 rows with f32 atomics; the
-//     kernel that consumes the moments finishes them (elementwise.hip *_fin kernels) -- no finalisation launch.
+//     kernel that consumes the moments finishes them (bn.hip *_fin kernels) -- no finalisation launch.
 //   * blockIdx -> tile: filter tile fastest (the blocks of XCD b%8 keep one filter slab in their L2), or,
 //     when the filter operand is small, one contiguous run of M tiles per XCD (halo rows shared in L2).
 #include "common.h"
@@ -673,7 +673,7 @@ static thread_local int g_last_plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 // Y2_BN_PART_ROWS (pixel tile, wave row) pairs get a row each (plain stores, one writer per element); larger grids wrap around
 // R rows with f32 atomic adds, R chosen for <= ~170 adds per address (the 104x104 layer; 20-90 elsewhere) and <= 128 rows to read.
 static thread_local int g_last_stat_rows = Y2_BN_PART_ROWS;
-// most rows the consumer's prologue accepts for Nf channels (elementwise.hip fin_shape_ok: rows x slice x 8 bytes <= 128 KB), <= 256
+// most rows the consumer's prologue accepts for Nf channels (bn.hip fin_shape_ok: rows x slice x 8 bytes <= 128 KB), <= 256
 static int y2_stat_rows_limit(int Nf, int vec) {
     int lpr = Nf / vec;
     if (lpr > 16) lpr = 16;

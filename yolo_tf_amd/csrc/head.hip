@@ -154,6 +154,12 @@ static int loss_impl(const void *logits, int ld, const float *anchors, const flo
     Y2_CHECK_LAUNCH();
     return YOLO2_OK;
 }
+// bytes of the caller-owned scratch `ws` of the loss entries: four partials per 256-lane workgroup + the four sums
+extern "C" size_t yolo2_loss_workspace_bytes(int B, int cells, int A) {
+    int lpc = 1;
+    while (lpc < A) lpc *= 2;
+    return (size_t)(4 * (((long)B * cells * lpc + 255) / 256) + 4) * sizeof(float);
+}
 extern "C" int yolo2_loss(const void *logits, int ld, const float *anchors, const float *mask, const float *prob,
                           const float *coords, const float *off_min, const float *off_max, const float *areas,
                           const float *hparam, float *objectives, void *dlogits, float *ws, int B, int cell_h,

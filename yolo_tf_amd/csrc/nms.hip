@@ -161,6 +161,8 @@ __global__ __launch_bounds__(256) void nms_kernel(float *__restrict__ conf, cons
     }
 }
 
+// bytes of the caller-owned scratch `ws` below: one int per (image, box, class)
+extern "C" size_t yolo2_nms_workspace_bytes(int B, int N, int C) { return (size_t)(B > 0 ? B : 0) * (size_t)(N > 0 ? N : 0) * (size_t)(C > 0 ? C : 0) * sizeof(int); }
 extern "C" int yolo2_nms(float *conf, const float *xy_min, const float *xy_max, int *order_out, int *ws, int B, int N, int C,
                          float threshold, float threshold_iou, void *stream) {
     Y2_CHECK_ARG(conf && xy_min && xy_max && ws);

@@ -3,7 +3,7 @@
 
 def reorg(net, stride=2, name='reorg'):
     """reference model/yolo2/function.py:22-29: stride-2 space-to-depth in tf.space_to_depth order (not Darknet's),
-    out[b, y, x, (sy*2+sx)*C + c] = in[b, 2y+sy, 2x+sx, c].  Adds the graph node; csrc/elementwise.hip reorg_kernel executes it and
+    out[b, y, x, (sy*2+sx)*C + c] = in[b, 2y+sy, 2x+sx, c].  Adds the graph node; csrc/layout.hip reorg_kernel executes it and
     writes straight into the concat buffer the result is re-homed in."""
     assert stride == 2 and net.h % 2 == 0 and net.w % 2 == 0
     g = net.graph

@@ -1,7 +1,7 @@
 """Optimizers and learning-rate schedule with the reference's configuration surface
 (train.py:70-80 get_optimizer, :116-124 exponential_decay; config.ini [optimizer_*],
 [exponential_decay]).  Each optimizer is ONE kernel launch over the flat parameter arena
-(csrc/elementwise.hip), with TF-1.0 Apply* update rules."""
+(csrc/optim.hip; Adam fused with the filter re-layout: csrc/filter_prep.hip), with TF-1.0 Apply* update rules."""
 import configparser
 import math
 

@@ -1,5 +1,5 @@
 """Detect-side image preprocessing (reference utils/preprocess.py:23-25, detect.py:33-38), run by
-csrc/elementwise.hip image kernels."""
+csrc/layout.hip image kernels."""
 import numpy as np
 import torch
 
