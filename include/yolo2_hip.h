@@ -733,6 +733,42 @@ size_t yolo2_histogram_result_bytes(int njobs);                    /* njobs * YO
 int yolo2_histogram_items(long long rows, int c, int ld, int dtype);   /* work items of one job (a count, not a status); 0 for an empty or malformed one */
 int yolo2_histogram(const yolo2_hist_job *jobs, int njobs, int items, void *out, size_t out_bytes, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- image summaries (new work): what the reference's train.py:44-53 asks tf.summary.image for, of many device images in one call.
+ * Specification: tests/image_summary_ref.py (TensorFlow 1.x core/kernels/summary_image_op.cc NormalizeFloatImage plus the reference's
+ * channel sum, restated; unpinned against TensorFlow).
+ *
+ * A job is ONE image of one tensor: `rows` = H*W pixels of `c` values every `ld` elements, `dtype` YOLO2_F32 or YOLO2_BF16 (widened to f32),
+ * `base` aligned to its element only (16-byte loads are used when base and ld allow them).  Lanes c <= j < ld of a pixel are padding or a
+ * concat neighbour and are never read.  depth = c for c in {1, 3, 4}; any other c is summed to ONE channel: f64, sequential from +0.0 inside
+ * each group of YOLO2_IMAGE_GROUP consecutive channels, the group partials added in ascending order to a total that starts at +0.0, one
+ * rounding to f32.  A pixel is finite when all its depth values are; image_min / image_max are taken over the values of the finite pixels
+ * (+inf / -inf when there are none); image_min < 0: scale = 127 / max(|min|, |max|) (0 if that is < 1e-6f), offset = 128; otherwise
+ * scale = 255 / image_max (0 if image_max < 1e-6f), offset = 0; byte = uint8(trunc(x * scale + offset)) with the product and the sum each
+ * rounded to f32; a non-finite pixel becomes (255, 0, 0, 255)[:depth].  rows = 0 is an empty job.
+ * out: njobs records of YOLO2_IMAGE_RECORD_BYTES {f32 image_min, f32 image_max, u32 non-finite pixels, f32 scale}, then the images: job j
+ * writes rows * depth bytes, packed [rows][depth], at byte `out_offset` from `out` (>= njobs * YOLO2_IMAGE_RECORD_BYTES; the ranges of two
+ * jobs must not overlap).  `sum_offset`: for a summed job, the index of its first f32 in the sums area of the workspace (rows floats,
+ * disjoint between jobs; ignored otherwise).  `first_item` is the sum of yolo2_image_summary_items() over the jobs before it; `items` of
+ * the call is that sum over all of them.  The job table lives in DEVICE memory; a malformed job, or one whose ranges leave out / ws, is
+ * treated as empty.  ws: yolo2_image_summary_workspace_bytes(njobs, sum of rows over the summed jobs), no initialisation needed.
+ * Every byte of a job's result depends on the job alone: min / max go through integer atomics on order-preserving keys, no float atomic is
+ * issued.  One call enqueues four operations whatever njobs is and never synchronises. */
+#define YOLO2_IMAGE_GROUP 8
+#define YOLO2_IMAGE_RECORD_BYTES 16
+typedef struct yolo2_image_job {
+    const void *base;
+    long long rows;
+    int c, ld, dtype;
+    int first_item;
+    long long out_offset;
+    long long sum_offset;
+} yolo2_image_job;
+size_t yolo2_image_summary_workspace_bytes(int njobs, long long sum_pixels);
+size_t yolo2_image_summary_result_bytes(int njobs, long long image_bytes);   /* njobs * YOLO2_IMAGE_RECORD_BYTES + image_bytes */
+int yolo2_image_summary_items(long long rows, int c, int ld, int dtype);      /* work items of one job (a count, not a status); 0 for an empty or malformed one */
+int yolo2_image_summary_depth(int c);                                          /* channels of the image made from c: c for 1, 3, 4, otherwise 1 (a count) */
+int yolo2_image_summary(const yolo2_image_job *jobs, int njobs, int items, void *out, size_t out_bytes, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- int8 inference (post-training quantisation; DESIGN.md section 15, specification: tests/quant_ref.py) -----------------------------
  * Symmetric int8 in -127 .. 127: q = clip(rint(x * inv_s), -127, 127) in f32, NaN -> 0, inv_s = float32(1) / s computed by the host.
  *

@@ -29,7 +29,7 @@ from yolo_tf_amd import checkpoint, tf_checkpoint, utils
 from yolo_tf_amd.utils import events
 from yolo_tf_amd.parallel import agree, init_distributed, sync_replicas
 from yolo_tf_amd.session import TrainSession
-from yolo_tf_amd.summary import HistogramSummaries
+from yolo_tf_amd.summary import HistogramSummaries, ImageSummaries
 from yolo_tf_amd.utils import data as udata
 
 
@@ -190,6 +190,9 @@ def main():
     # [summary] histogram / gradients (the reference's summary_histogram and summarize_gradients): rank 0 bins its own replica's tensors on the
     # device after a summarised step; with both keys unset nothing is allocated or launched
     histograms = HistogramSummaries(session, config) if rank == 0 else None
+    # [summary] image / image_max (the reference's summary_image): the first image_max images of every matched stored activation, made into
+    # bytes on the device in the same place; disabled (a missing key, as in the default config) nothing is allocated or launched
+    images_summary = ImageSummaries(session, config) if rank == 0 else None
     save = (lambda: tf_checkpoint.save(logdir, session)) if args.ckpt_format == 'tf' else (lambda: checkpoint.save(logdir, session))
     last_summary = last_save = t_rate = time.time()
     n_rate = 0
@@ -219,6 +222,8 @@ def main():
         if want_summary:
             if histograms is not None and histograms.enabled:
                 histograms.collect()             # asynchronous: binned and copied behind the step, read after fetch() below
+            if images_summary is not None and images_summary.enabled:
+                images_summary.collect()         # likewise
             s = session.fetch()
             shard_error = None
             if hasattr(data, 'pipe'):
@@ -234,6 +239,8 @@ def main():
                 writer.add_training_summary(session.global_step, s)
                 if histograms.enabled:
                     histograms.write(writer, session.global_step)
+                if images_summary.enabled:
+                    images_summary.write(writer, session.global_step)
                 writer.flush()
                 logging.warning('step %d: total_loss=%.6f iou_best=%.6f iou_normal=%.6f coords=%.6f prob=%.6f (%.1f img/s)'
                                 % (session.global_step, s['total_loss'], s['iou_best'], s['iou_normal'], s['coords'], s['prob'], rate))

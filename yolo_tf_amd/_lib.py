@@ -110,6 +110,7 @@ SIGNATURES = {
     'yolo2_anchor_assign': [_p, _i, _p, _p, _i, _i, _p, ctypes.c_size_t, _p, _p, _p],
     'yolo2_anchor_update': [_p, _p, _i, _i, _p, ctypes.c_size_t, _i, _p, _p, _p, _p, _p],
     'yolo2_histogram': [_p, _i, _i, _p, ctypes.c_size_t, _p, ctypes.c_size_t, _p],
+    'yolo2_image_summary': [_p, _i, _i, _p, ctypes.c_size_t, _p, ctypes.c_size_t, _p],
     'yolo2_conv2d_i8': [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, _p],
     'yolo2_absmax': [_p, _i, _p, _p],
     'yolo2_quantize': [_p, _i, _p, _i, _l, _i, _f, _i, _p],
@@ -162,6 +163,10 @@ QUERIES = {
     'yolo2_histogram_workspace_bytes': (ctypes.c_size_t, [_i]),
     'yolo2_histogram_result_bytes': (ctypes.c_size_t, [_i]),
     'yolo2_histogram_items': (_i, [ctypes.c_longlong, _i, _i, _i]),        # a count, not a status
+    'yolo2_image_summary_workspace_bytes': (ctypes.c_size_t, [_i, ctypes.c_longlong]),
+    'yolo2_image_summary_result_bytes': (ctypes.c_size_t, [_i, ctypes.c_longlong]),
+    'yolo2_image_summary_items': (_i, [ctypes.c_longlong, _i, _i, _i]),    # a count, not a status
+    'yolo2_image_summary_depth': (_i, [_i]),                               # a count, not a status
 }
 
 
@@ -175,6 +180,12 @@ class AugmentParams(ctypes.Structure):
 class HistJob(ctypes.Structure):
     """yolo2_hist_job of include/yolo2_hip.h"""
     _fields_ = [('base', ctypes.c_void_p), ('rows', ctypes.c_longlong), ('c', _i), ('ld', _i), ('dtype', _i), ('first_item', _i)]
+
+
+class ImageJob(ctypes.Structure):
+    """yolo2_image_job of include/yolo2_hip.h"""
+    _fields_ = [('base', ctypes.c_void_p), ('rows', ctypes.c_longlong), ('c', _i), ('ld', _i), ('dtype', _i), ('first_item', _i),
+                ('out_offset', ctypes.c_longlong), ('sum_offset', ctypes.c_longlong)]
 
 
 class AbsmaxJob(ctypes.Structure):

@@ -33,6 +33,7 @@ SOURCES = {
     'eval_coco.hip': ['-ffp-contract=off'],
     'anchors.hip': ['-ffp-contract=off'],
     'summary.hip': ['-ffp-contract=off'],
+    'image_summary.hip': ['-ffp-contract=off'],
     'conv_i8.hip': ['-ffp-contract=off'],
     'quant.hip': ['-ffp-contract=off'],
 }

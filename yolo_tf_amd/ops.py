@@ -676,6 +676,75 @@ def decode_histograms(words):
     return out
 
 
+IMAGE_RECORD_BYTES = 16    # YOLO2_IMAGE_RECORD_BYTES of include/yolo2_hip.h
+
+
+def image_depth(c):
+    """Channels of the image yolo2_image_summary makes from ``c``: c for 1, 3, 4, otherwise 1 (the channel sum)."""
+    return int(_lib.query('yolo2_image_summary_depth', int(c)))
+
+
+class ImageJobs(object):
+    """Device job table of yolo2_image_summary, built once for a fixed list of images, with its result and workspace buffers.
+
+    ``jobs``: [(tensor, rows, c, ld)] -- one IMAGE each: ``tensor`` a contiguous f32 / bf16 device tensor (a view is fine: its data_ptr() is the
+    job's base) of which the job reads ``rows`` = H*W pixels of ``c`` values every ``ld`` elements; rows = 0 is an empty job.  The extents are
+    checked against the tensors here, so the kernel never reads past one.  The result is ONE uint8 buffer ``out``: the records, then every
+    job's packed [rows][depth] bytes at ``offsets[j]`` (16-byte aligned).  The tensors are kept alive by this object."""
+
+    def __init__(self, jobs, device=None):
+        from ._lib import ImageJob
+        assert len(jobs) > 0
+        self.tensors = [j[0] for j in jobs]
+        self.device = device if device is not None else self.tensors[0].device
+        self.n = len(jobs)
+        arr = (ImageJob * self.n)()
+        first, sums, off = 0, 0, self.n * IMAGE_RECORD_BYTES
+        self.inputs, self.shapes, self.offsets = [], [], []         # (rows, c, ld) read / (rows, depth) written / byte offset in out
+        for d, (t, rows, c, ld) in zip(arr, jobs):
+            rows, c, ld = int(rows), int(c), int(ld)
+            assert t.is_cuda and t.is_contiguous() and 0 <= c <= ld and 0 <= rows < 2 ** 31, (rows, c, ld)
+            extent = (rows - 1) * ld + c if rows > 0 and c > 0 else 0
+            assert extent <= t.numel(), 'image job of %d elements on a tensor of %d' % (extent, t.numel())
+            if extent == 0:
+                rows, c, ld = 0, 0, 0
+            depth = image_depth(c)
+            summed = c > 0 and depth != c
+            d.base, d.rows, d.c, d.ld, d.dtype, d.first_item = (t.data_ptr() if extent else None), rows, c, ld, dtype_code(t.dtype), first
+            d.out_offset, d.sum_offset = off, (sums if summed else 0)
+            self.inputs.append((rows, c, ld))
+            self.shapes.append((rows, depth))
+            self.offsets.append(off)
+            first += int(_lib.query('yolo2_image_summary_items', rows, c, ld, d.dtype))
+            sums += rows if summed else 0
+            off += (rows * depth + 15) // 16 * 16
+        self.items = first
+        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
+        nbytes = int(_lib.query('yolo2_image_summary_result_bytes', self.n, off - self.n * IMAGE_RECORD_BYTES))
+        assert nbytes == off
+        self.out = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        self.ws = torch.empty(max(int(_lib.query('yolo2_image_summary_workspace_bytes', self.n, sums)) // 4, 1), dtype=torch.int32, device=self.device)
+
+    def launch(self):
+        """Enqueues the call on the current stream (no synchronisation); records and images are in ``self.out`` once it has run."""
+        call('yolo2_image_summary', ptr(self.table), self.n, self.items, ptr(self.out), self.out.numel(), ptr(self.ws), self.ws.numel() * 4, _stream())
+        return self.out
+
+
+def decode_images(buf, shapes, offsets):
+    """Host view of yolo2_image_summary's result: ``buf`` a uint8 array (numpy) as ImageJobs.out, ``shapes`` / ``offsets`` of the same table.
+    -> [(record dict with min, max, scale (float) and nonfinite (int), uint8 array [rows][depth])]."""
+    buf = np.ascontiguousarray(buf)
+    n = len(shapes)
+    rec = buf[:n * IMAGE_RECORD_BYTES].view(np.uint32).reshape(n, 4)
+    f = rec.view(np.float32)
+    out = []
+    for j, ((rows, depth), off) in enumerate(zip(shapes, offsets)):
+        out.append(({'min': float(f[j, 0]), 'max': float(f[j, 1]), 'nonfinite': int(rec[j, 2]), 'scale': float(f[j, 3])},
+                    buf[off:off + rows * depth].reshape(rows, depth)))
+    return out
+
+
 # ---- int8 inference (include/yolo2_hip.h "int8 inference"; specification: tests/quant_ref.py) ----------------------------------------
 
 I8_OUT_I8, I8_OUT_BF16, I8_OUT_F32, I8_OUT_ACC = _lib.I8_OUT_I8, _lib.I8_OUT_BF16, _lib.I8_OUT_F32, _lib.I8_OUT_ACC

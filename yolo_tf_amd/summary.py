@@ -18,7 +18,11 @@ replicas when nothing is clipped -- the update applies the 1 / world factor itse
 add_gradients_summaries is restated from memory: DESIGN.md.)
 
 A missing section or key means disabled -- the reference's default config spells the key ``histogram_``, which disables it the same
-way -- and then nothing is allocated and nothing is launched."""
+way -- and then nothing is allocated and nothing is launched.
+
+Image summaries: the reference's ``[summary] image`` and ``image_max`` keys (train.py:44-53 there) select activations by the same names and
+hand them to ``tf.summary.image``; here yolo2_image_summary (csrc/image_summary.hip) makes the bytes of the first ``image_max`` images of
+every matched, stored activation on the device (ImageSummaries below), and utils/png.py wraps them."""
 import logging
 import math
 import re
@@ -189,3 +193,125 @@ class HistogramSummaries(object):
                                  'bucket_limit': limit, 'bucket': bucket}))
         writer.add_histograms(step, protos, scalars=scalars or None)
         return len(protos)
+
+
+def read_image_config(config):
+    """-> (image pattern, image_max) from the reference's own keys, or (None, None) when either is missing: the reference's summary_image
+    catches NoSectionError / NoOptionError of both ``config.get('summary', 'image')`` and ``config.getint('summary', 'image_max')``."""
+    if config is None or not config.has_section('summary') or not config.has_option('summary', 'image'):
+        return None, None
+    pattern = config.get('summary', 'image').strip() or None
+    if pattern is None or not config.has_option('summary', 'image_max'):
+        return None, None
+    image_max = config.getint('summary', 'image_max')
+    if image_max < 1:
+        raise ValueError('[summary] image_max = %d: tf.summary.image needs max_outputs >= 1' % image_max)
+    return pattern, image_max
+
+
+def image_tags(name, image_max, batch):
+    """tf.summary.image's tags: ``<name>/image`` when max_outputs is 1, otherwise ``<name>/image/<i>`` for the first min(max_outputs, batch)."""
+    return [name + '/image'] if image_max == 1 else ['%s/image/%d' % (name, i) for i in range(min(image_max, batch))]
+
+
+class ImageSummaries(object):
+    def __init__(self, session, config):
+        self.session = session
+        self.pattern, self.image_max = read_image_config(config)
+        self.enabled = self.pattern is not None
+        if not self.enabled:
+            logging.warning('summary_image disabled')         # (the reference's words for a missing section or key)
+        self._plans = {}           # bound input size -> (meta [(tag, h, w, depth)], ops.ImageJobs, pinned host buffer)
+        self._pending = None
+        self._warned = set()
+        self.records = []          # [(tag, record)] of the last results(): image_min, image_max, scale, non-finite pixels
+
+    def resolve(self, graph=None):
+        """-> [(name, graph Tensor)] of the activations the pattern selects, in graph order (pure host logic).  Variables and batch moments the
+        pattern also matches are not images here: one warning, then skipped."""
+        if not self.enabled:
+            return []
+        graph = graph if graph is not None else self.session.engine.graph
+        prog = re.compile(self.pattern)
+        matched = [n for n in summarizable_names(graph) if prog.match(n[0])]
+        others = [tag for tag, kind, _ in matched if kind != 'activation']
+        if others and 'others' not in self._warned:
+            self._warned.add('others')
+            logging.warning('[summary] image: %d matched variable(s) / batch moment(s) are not images and are skipped: %s',
+                            len(others), ', '.join(others[:8]) + (' ...' if len(others) > 8 else ''))
+        return [(tag, ref) for tag, kind, ref in matched if kind == 'activation']
+
+    def _plan(self):
+        from . import ops
+        e = self.session.engine
+        key = id(e._cur)
+        if key in self._plans:
+            return self._plans[key]
+        import torch
+        stored = dict((t, where) for t, where in e.summarizable_tensors())
+        meta, jobs, missing = [], [], []
+        for name, t in self.resolve(e.graph):
+            if stored.get(t) is None:
+                missing.append(name)
+                continue
+            buf, rows, c, ld = stored[t]
+            batch, pixels = rows // (t.h * t.w), t.h * t.w
+            assert batch * pixels == rows and c == t.c, (name, rows, t.h, t.w, c)
+            for i, tag in enumerate(image_tags(name, self.image_max, batch)):
+                meta.append((tag, t.h, t.w, ops.image_depth(c)))
+                jobs.append((buf[i * pixels * ld:], pixels, c, ld))
+        if missing and 'missing' not in self._warned:
+            self._warned.add('missing')
+            logging.warning('[summary] image: %d matched tensor(s) are never stored by the training forward and are skipped: %s',
+                            len(missing), ', '.join(missing[:8]) + (' ...' if len(missing) > 8 else ''))
+        if not jobs:
+            if 'empty' not in self._warned:
+                self._warned.add('empty')
+                logging.warning('[summary] image = %r selects nothing that can be summarised: image summaries disabled', self.pattern)
+            plan = (meta, None, None)
+        else:
+            table = ops.ImageJobs(jobs, device=e.device)
+            host = torch.empty(table.out.shape, dtype=torch.uint8).pin_memory()
+            plan = (meta, table, host)
+        self._plans[key] = plan
+        return plan
+
+    def collect(self):
+        """Enqueues the call and ONE asynchronous copy of records and bytes to pinned host memory on the current stream; no synchronisation.
+        Call it after a step, before the next one overwrites the activations."""
+        if not self.enabled:
+            return
+        import torch
+        meta, table, host = self._plan()
+        if table is None:
+            return
+        table.launch()
+        host.copy_(table.out, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        self._pending = (meta, table, host, done)
+
+    def results(self):
+        """Waits for the last collect() and returns [(tag, height, width, depth, uint8 array [height][width][depth])]."""
+        from . import ops
+        if self._pending is None:
+            return []
+        meta, table, host, done = self._pending
+        self._pending = None
+        done.synchronize()
+        decoded = ops.decode_images(host.numpy().copy(), table.shapes, table.offsets)      # (a copy: the pinned buffer is the next collection's destination)
+        self.records = [(m[0], rec) for m, (rec, _) in zip(meta, decoded)]
+        return [(tag, h, w, depth, pix.reshape(h, w, depth)) for (tag, h, w, depth), (_, pix) in zip(meta, decoded)]
+
+    def write(self, writer, step):
+        """PNG-encodes the collected images and appends them to ``writer`` as one event of ``step``."""
+        from .utils import png
+        images = self.results()
+        if not images:
+            return 0
+        for tag, rec in self.records:
+            if rec['nonfinite']:
+                logging.warning('image summary %s: %d pixel(s) with NaN / Inf drawn in the bad colour', tag, rec['nonfinite'])
+        writer.add_images(step, [(tag, {'height': h, 'width': w, 'colorspace': depth, 'encoded_image_string': png.encode(pix)})
+                                 for tag, h, w, depth, pix in images])
+        return len(images)

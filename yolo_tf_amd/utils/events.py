@@ -3,15 +3,17 @@
 The reference hands ``slim.learning.train`` a ``tf.summary.FileWriter(os.path.join(logdir, args.logname))`` (train.py:141-145)
 and summarises the scalars its ``[summary] scalar`` pattern selects (config.ini:63, train.py:31-41): ``total_loss`` and
 ``total_loss/objectives/{iou_best,iou_normal,coords,prob}``.  This module writes the same kind of file -- TFRecord framing
-(utils/tfrecord.py) around serialized ``tensorflow.Event`` protos -- for exactly those scalars, hand-rolling the three tiny
+(utils/tfrecord.py) around serialized ``tensorflow.Event`` protos -- for exactly those scalars, hand-rolling the few tiny
 messages it needs:
 
     Event   { double wall_time = 1; int64 step = 2; oneof { string file_version = 3; Summary summary = 5; } }
-    Summary { repeated Value value = 1; }      Value { string tag = 1; float simple_value = 2; HistogramProto histo = 5; }
+    Summary { repeated Value value = 1; }      Value { string tag = 1; float simple_value = 2; Image image = 4; HistogramProto histo = 5; }
+    Image { int32 height = 1; int32 width = 2; int32 colorspace = 3; bytes encoded_image_string = 4; }
     HistogramProto { double min = 1, max = 2, num = 3, sum = 4, sum_squares = 5; repeated double bucket_limit = 6 [packed], bucket = 7 [packed]; }
 
 TensorBoard reads it like any ``events.out.tfevents.*`` file.  Histogram summaries (train.py:56-61 of the reference, ``[summary] histogram``
-and ``gradients``) come from yolo_tf_amd/summary.py; image summaries (train.py:44-53) are not produced.  Host-side I/O only."""
+and ``gradients``) and image summaries (train.py:44-53, ``[summary] image`` and ``image_max``) come from yolo_tf_amd/summary.py; the images
+are PNGs written by utils/png.py.  Host-side I/O only."""
 import os
 import socket
 import struct
@@ -77,20 +79,56 @@ def decode_histogram(buf):
     return out
 
 
-def encode_event(wall_time, step=None, file_version=None, scalars=None, histograms=None):
-    """``histograms``: [(tag, dict for encode_histogram)], written after the scalars into the same Summary; None (or empty with no scalars)
-    leaves the bytes of a scalar-only event exactly as they were."""
+def encode_image(im):
+    """Summary.Image bytes of ``im``: a dict with height, width, colorspace (the channel count: 1 grey, 3 RGB, 4 RGBA) and
+    encoded_image_string (PNG bytes).  proto3 rules: a field equal to zero / empty is not written."""
+    out = b''
+    for field, key in ((1, 'height'), (2, 'width'), (3, 'colorspace')):
+        if int(im[key]) != 0:
+            out += _varint((field << 3) | 0) + _varint(int(im[key]))
+    if len(im['encoded_image_string']):
+        out += _ld(4, bytes(im['encoded_image_string']))
+    return out
+
+
+def decode_image(buf):
+    out = {'height': 0, 'width': 0, 'colorspace': 0, 'encoded_image_string': b''}
+    keys = {1: 'height', 2: 'width', 3: 'colorspace'}
+    i = 0
+    while i < len(buf):
+        key, i = _read_varint(buf, i)
+        f, wt = key >> 3, key & 7
+        if wt == 0:
+            v, i = _read_varint(buf, i)
+            if f in keys:
+                out[keys[f]] = v
+        elif wt == 2:
+            n, i = _read_varint(buf, i)
+            if f == 4:
+                out['encoded_image_string'] = bytes(buf[i:i + n])
+            i += n
+        else:
+            raise ValueError('wire type %d in a Summary.Image' % wt)
+    return out
+
+
+def encode_event(wall_time, step=None, file_version=None, scalars=None, histograms=None, images=None):
+    """``histograms``: [(tag, dict for encode_histogram)], written after the scalars into the same Summary; ``images``: [(tag, dict for
+    encode_image)], written after the histograms.  None (or empty with no scalars) leaves the bytes of a scalar-only event exactly as they
+    were."""
     ev = _varint((1 << 3) | 1) + struct.pack('<d', float(wall_time))
     if step is not None and step != 0:
         ev += _varint((2 << 3) | 0) + _varint(int(step))
     if file_version is not None:
         ev += _ld(3, file_version.encode())
-    if scalars is not None or histograms:
+    if scalars is not None or histograms or images:
         summary = b''
         for tag, value in (scalars or ()):
             summary += _ld(1, _ld(1, tag.encode()) + _varint((2 << 3) | 5) + struct.pack('<f', float(value)))
         for tag, h in (histograms or ()):
             summary += _ld(1, _ld(1, tag.encode()) + _ld(5, encode_histogram(h)))
+        for tag, im in (images or ()):
+            summary += _ld(1, _ld(1, tag.encode()) + _ld(4, encode_image(im)))
         ev += _ld(5, summary)
     return ev
 
@@ -115,7 +153,7 @@ def decode_event(buf):
                 raise ValueError('wire type %d' % wt)
             yield f, wt, v
 
-    out = {'step': 0, 'scalars': [], 'histograms': []}
+    out = {'step': 0, 'scalars': [], 'histograms': [], 'images': []}
     for f, wt, v in fields(buf):
         if f == 1:
             out['wall_time'] = struct.unpack('<d', v)[0]
@@ -126,16 +164,20 @@ def decode_event(buf):
         elif f == 5:
             for f2, _, val in fields(v):
                 if f2 == 1:
-                    tag, simple, histo = None, None, None
+                    tag, simple, histo, image = None, None, None, None
                     for f3, _, x in fields(val):
                         if f3 == 1:
                             tag = x.decode()
                         elif f3 == 2:
                             simple = struct.unpack('<f', x)[0]
+                        elif f3 == 4:
+                            image = decode_image(x)
                         elif f3 == 5:
                             histo = decode_histogram(x)
                     if histo is not None:
                         out['histograms'].append((tag, histo))
+                    elif image is not None:
+                        out['images'].append((tag, image))
                     else:
                         out['scalars'].append((tag, simple))
     return out
@@ -174,6 +216,10 @@ class FileWriter(object):
     def add_histograms(self, step, histograms, scalars=None, wall_time=None):
         """histograms: [(tag, dict for encode_histogram)]; ``scalars`` (optional [(tag, float)]) go into the same event."""
         self._write(encode_event(time.time() if wall_time is None else wall_time, step=step, scalars=scalars, histograms=list(histograms)))
+
+    def add_images(self, step, images, wall_time=None):
+        """images: [(tag, dict for encode_image)], one event."""
+        self._write(encode_event(time.time() if wall_time is None else wall_time, step=step, images=list(images)))
 
     def add_training_summary(self, step, fetched):
         """The five scalars of the reference's [summary] section from TrainSession.fetch()'s dict."""
