@@ -96,7 +96,7 @@ def main():
     if model_path is None and tf_path is None:
         raise FileNotFoundError('no checkpoint in ' + logdir)
     logging.info('load ' + (model_path or tf_path))
-    step = checkpoint.restore(model_path, engine=sess.engine) if model_path else tf_checkpoint.restore(tf_path, engine=sess.engine)
+    step = checkpoint.restore(model_path, engine=sess.engine, ema=args.ema) if model_path else tf_checkpoint.restore(tf_path, engine=sess.engine, ema=args.ema)
     logging.info('global_step=%d' % step)
     path = os.path.expanduser(os.path.expandvars(args.path))
     paths = [path] if os.path.isfile(path) else [os.path.join(d, f) for d, _, fs in os.walk(path) for f in fs
@@ -123,6 +123,7 @@ def make_args():
     parser.add_argument('--output', help='directory for annotated images (the reference opens a matplotlib window instead)')
     parser.add_argument('--dtype', default=None, choices=['bf16', 'f32', 'int8'], help="'int8': post-training quantised inference (needs a calibration)")
     parser.add_argument('--calibration', default=None, help='--dtype int8: the file quantize.py wrote (default: calibration.npz in the logdir)')
+    parser.add_argument('--ema', action='store_true', help='use the moving averages of the weights a run with [mi355x] ema_decay keeps in its checkpoints')
     return parser.parse_args()
 
 

@@ -62,7 +62,7 @@ def main():
     if model_path is None and tf_path is None:
         raise FileNotFoundError('no checkpoint in ' + logdir)
     logging.info('load ' + (model_path or tf_path))
-    step = checkpoint.restore(model_path, engine=sess.engine) if model_path else tf_checkpoint.restore(tf_path, engine=sess.engine)
+    step = checkpoint.restore(model_path, engine=sess.engine, ema=args.ema) if model_path else tf_checkpoint.restore(tf_path, engine=sess.engine, ema=args.ema)
     logging.info('global_step=%d' % step)
     images, objects, difficult, crowd, area = load_data(args, config, len(builder.names))
     m = sess.model
@@ -70,7 +70,7 @@ def main():
                              crowd=crowd, area=area)
     result = evaluate.evaluate(builder, sess, data, mode=args.mode, threshold=args.threshold, threshold_iou=args.threshold_iou, iou=args.iou,
                                preprocess_mode=PREPROCESS[args.preprocess], max_records=args.max_records, protocol=args.protocol)
-    extra = dict(names=list(builder.names), images=len(images), checkpoint=model_path or tf_path, global_step=int(step), calibration=calibration,
+    extra = dict(names=list(builder.names), images=len(images), checkpoint=model_path or tf_path, global_step=int(step), calibration=calibration, ema=bool(args.ema),
                  config={k: getattr(args, k) for k in ('config', 'profile', 'data', 'batch_size', 'threshold', 'threshold_iou', 'iou', 'mode', 'protocol',
                                                        'preprocess', 'dtype', 'limit', 'images', 'seed')})
     if args.protocol == 'coco':
@@ -117,6 +117,7 @@ def make_args(argv=None):
     parser.add_argument('--max_records', type=int, default=None, help='capacity of the record buffer (default: the worst case of the mode)')
     parser.add_argument('--dtype', default=None, choices=['bf16', 'f32', 'int8'], help="'int8': post-training quantised inference (needs a calibration)")
     parser.add_argument('--calibration', default=None, help='--dtype int8: the file quantize.py wrote (default: calibration.npz in the logdir)')
+    parser.add_argument('--ema', action='store_true', help='use the moving averages of the weights a run with [mi355x] ema_decay keeps in its checkpoints')
     parser.add_argument('--level', default='info', help='logging level')
     return parser.parse_args(argv)
 

@@ -438,6 +438,10 @@ int yolo2_adadelta(float *w, const float *g, float *acc, float *acc_update, long
  * accum starts at initial_accumulator_value, linear at 0; lr_power <= 0 (-0.5 takes the sqrt form) */
 int yolo2_ftrl(float *w, const float *g, float *accum, float *linear, long n, float lr, float lr_power,
                float l1, float l2, float gscale, void *stream);
+/* tf.train.ExponentialMovingAverage's assign_moving_average over a flat f32 arena: ema -= (ema - w) * one_minus_decay, per element
+ * d = ema - w; d = d * one_minus_decay; ema = ema - d, each rounded once in f32 (no FMA), NaN / inf propagating.  One launch; any n >= 1 and any
+ * 4-byte aligned pointers (16-byte accesses where both are 16-byte aligned at the same element); 0 <= one_minus_decay <= 1. */
+int yolo2_ema_update(float *ema, const float *w, long n, float one_minus_decay, void *stream);
 /* x *= scale (1/world averaging of the all-reduced gradient ahead of clip_by_norm) */
 int yolo2_scale(float *x, long n, float scale, void *stream);
 /* x[a:b] = 0 for nranges half-open element ranges given as a HOST array {a0,b0,a1,b1,...}: the accumulating filter

@@ -33,7 +33,7 @@ def main():
     if model_path is None and tf_path is None:
         raise FileNotFoundError('no checkpoint in ' + logdir)
     logging.info('load ' + (model_path or tf_path))
-    step = checkpoint.restore(model_path, engine=sess.engine) if model_path else tf_checkpoint.restore(tf_path, engine=sess.engine)
+    step = checkpoint.restore(model_path, engine=sess.engine, ema=args.ema) if model_path else tf_checkpoint.restore(tf_path, engine=sess.engine, ema=args.ema)
     images, objects = load_data(args, config, len(builder.names))[:2]
     m = sess.model
     data = evaluate.EvalData(images, objects, args.batch_size, builder.width, builder.height, m.cell_width, m.cell_height)
@@ -61,6 +61,7 @@ def make_args(argv=None):
     parser.add_argument('-o', '--output', default=None, help='calibration file (default: calibration.npz in the logdir, beside the checkpoint)')
     parser.add_argument('--images', type=int, default=None, help='--data synthetic: number of images (default: batches * batch size)')
     parser.add_argument('--seed', type=int, default=0, help='--data synthetic: seed')
+    parser.add_argument('--ema', action='store_true', help='use the moving averages of the weights a run with [mi355x] ema_decay keeps in its checkpoints')
     parser.add_argument('--level', default='info', help='logging level')
     args = parser.parse_args(argv)
     args.limit = args.batches * args.batch_size

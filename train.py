@@ -138,7 +138,8 @@ def main():
                            sync_bn=config.getboolean('mi355x', 'sync_bn') if config.has_option('mi355x', 'sync_bn') else False,
                            shard_optimizer=config.getboolean('mi355x', 'shard_optimizer') if config.has_option('mi355x', 'shard_optimizer') else False,
                            deterministic=True if args.deterministic else None)      # (None: [mi355x] deterministic / YOLO2_DETERMINISTIC decide)
-    logging.warning('optimizer=%s, dtype=%s, world=%d, parameters=%d' % (args.optimizer, dtype, world, session.engine.n_params))
+    logging.warning('optimizer=%s, dtype=%s, world=%d, parameters=%d%s' % (args.optimizer, dtype, world, session.engine.n_params,
+                                                                          ', ema_decay=%g' % session.ema_decay if session.ema is not None else ''))
     # rank 0 alone chooses and reads the checkpoint; the others receive parameters, statistics, optimizer slots and
     # global_step from it (same seed -> same initial weights anyway, but a restore must not depend on what each rank sees)
     # Both containers may sit in one logdir (a run resumed with the other --ckpt_format, or a logdir the reference wrote): the one

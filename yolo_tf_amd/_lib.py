@@ -93,6 +93,7 @@ SIGNATURES = {
     'yolo2_clip_by_norm_fixed': [_p, _p, _i, _f, _p, ctypes.c_size_t, _p],
     'yolo2_ftrl': [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _p],
     'yolo2_scale': [_p, _l, _f, _p],
+    'yolo2_ema_update': [_p, _p, _l, _f, _p],
     'yolo2_zero_ranges': [_p, _p, _i, _p],
     'yolo2_bn_fold': [_p, _p, _p, _p, _p, _p, _p, _l, _i, _f, _p],
     'yolo2_selftest_tr16': [_p, _p],

@@ -366,6 +366,11 @@ def scale(x, n, s):
     call('yolo2_scale', ptr(x), n, s, _stream())
 
 
+def ema_update(ema, w, n, one_minus_decay):
+    """ema -= (ema - w) * one_minus_decay over ``n`` f32 elements (tf.train.ExponentialMovingAverage's assign_moving_average), one launch."""
+    call('yolo2_ema_update', ptr(ema), ptr(w), n, one_minus_decay, _stream())
+
+
 def zero_ranges(x, ranges):
     """x[a:b] = 0 for every (a, b) in ``ranges`` (element offsets; host list)."""
     flat = (ctypes.c_long * (2 * len(ranges)))(*[int(v) for ab in ranges for v in ab])

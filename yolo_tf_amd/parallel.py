@@ -39,7 +39,8 @@ def sync_replicas(session, src=0, always=False):
     if not dist.is_initialized() or (dist.get_world_size() == 1 and not always):
         return
     e = session.engine
-    for t in [e.params, e.state] + list(session.optimizer.slots):
+    ema = getattr(session, 'ema', None)        # the weight average ([mi355x] ema_decay), when the session keeps one
+    for t in [e.params, e.state] + list(session.optimizer.slots) + ([ema] if ema is not None else []):
         dist.broadcast(t, src=src)
     step = torch.tensor([session.global_step], dtype=torch.int64, device=e.params.device)
     dist.broadcast(step, src=src)

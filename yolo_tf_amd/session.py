@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .engine import Engine, layer_end_offsets
+from .engine import Engine, layer_end_offsets, staggered
 from .graph import pad8
 from .model.yolo2 import OBJECTIVE_KEYS
 from .optim import Optimizer, learning_rate_fn
@@ -18,6 +18,22 @@ def _label_shapes(B, cells, C):
     return [(B, cells), (B, cells, C), (B, cells, 4), (B, cells, 2), (B, cells, 2), (B, cells)]
 
 
+def ema_decay_option(ema_decay, config):
+    """The ``ema_decay`` of a TrainSession as a float: the argument, or ``[mi355x] ema_decay`` of the config when the argument is None; absent or 0 = off
+    (returned as 0.0).  Anything outside [0, 1) raises ValueError.  Pure host logic."""
+    if ema_decay is None:
+        ema_decay = config.getfloat('mi355x', 'ema_decay') if config is not None and config.has_option('mi355x', 'ema_decay') else 0.0
+    decay = float(ema_decay)
+    if not 0.0 <= decay < 1.0:
+        raise ValueError('ema_decay = %r: the decay of the weight average lies in [0, 1) (0 or absent: off)' % (ema_decay,))
+    return decay
+
+
+def ema_decay_at(ema_decay, t):
+    """[TF-sem] tf.train.ExponentialMovingAverage(decay, num_updates=t): min(decay, (1 + t) / (10 + t)), in Python floats."""
+    return min(ema_decay, (1.0 + t) / (10.0 + t))
+
+
 class TrainSession(object):
     """One training replica.  ``step`` = per-image standardisation -> forward (batch-stat BN, EMA
     update first: [TF-sem] UPDATE_OPS) -> loss + its gradient -> backward -> (all-reduce) -> optional
@@ -25,15 +41,19 @@ class TrainSession(object):
 
     def __init__(self, builder, batch_size, dtype='bf16', optimizer='adam', learning_rate=1e-6, gradient_clip=0.0,
                  config=None, seed=0, world_size=1, bucket_mb=64.0, preprocess_mode=0, sizes=None, grad_dtype='f32', comm_cus=None, comm_timing=False,
-                 sync_bn=False, shard_optimizer=False, deterministic=None):
+                 sync_bn=False, shard_optimizer=False, deterministic=None, ema_decay=None):
         """``sizes``: optional list of (width, height) input sizes for multi-scale training (BASELINE configs[3]); buffers are
         allocated once for the largest, ``set_size`` switches between them, the builder's configured size is selected first.
 
         ``deterministic``: bitwise reproducible steps (deterministic training mode) -- same parameters, optimizer slots, BN state,
         global_step, image tensor and labels => bitwise the same state after ``step()``, whatever the buffer addresses, the process or the
         run.  None (default): on when ``[mi355x] deterministic`` of the config is true or YOLO2_DETERMINISTIC=1 is set; False / True decide here.  YOLOv2
-        family only; with world_size > 1 the local computation is deterministic but nothing is promised across the collective."""
+        family only; with world_size > 1 the local computation is deterministic but nothing is promised across the collective.
+
+        ``ema_decay``: exponential moving average of the trainable arena (weight averaging), updated once per step after the optimizer.
+        None (default): ``[mi355x] ema_decay`` of the config; absent or 0: off -- ``session.ema`` is None, nothing is allocated or launched."""
         assert builder.training, 'call builder(data, training=True) first'
+        self.ema_decay = ema_decay_option(ema_decay, config if config is not None else getattr(builder, 'config', None))
         self.builder = builder
         self.B = batch_size
         own = (builder.width, builder.height)
@@ -124,6 +144,13 @@ class TrainSession(object):
         self.async_errors = ops.AsyncErrorPoll() if dev.type == 'cuda' else None
         # arena offset below which every gradient is final once a given layer's backward has run
         self._layer_end = layer_end_offsets(e.graph, e.param_offsets)
+        # [TF-sem] tf.train.ExponentialMovingAverage: one shadow per trainable variable, at the variable's own range of an arena laid out like
+        # engine.params, starting at the variable's initial value (no zero-debias).  The BN moving statistics (engine.state) are averages already.
+        self.ema, self.ema_var = None, {}
+        if self.ema_decay > 0:
+            self.ema = staggered(e.n_params, torch.float32, dev)
+            self.ema.copy_(e.params)
+            self.ema_var = {name: self.ema[o:o + n] for name, (o, n) in e.param_offsets.items()}
 
     def set_size(self, width, height):
         """Input size of the following steps (one of the sizes the session was built with); weights, statistics, optimizer state
@@ -210,6 +237,7 @@ class TrainSession(object):
             torch.cuda.current_stream().wait_stream(self.opt_stream)
             e.adam_update_small(self.optimizer.slots[0], self.optimizer.slots[1], alpha, b1, b2, eps, 1.0)
             self.global_step += 1
+            self._update_ema()
             return
         if self.reducer is not None and getattr(self, '_sharded_pending', False):
             # the buckets' chains (reduce-scatter, shard update, all-gather) were enqueued during backward: wait for the last of them
@@ -235,6 +263,19 @@ class TrainSession(object):
             self.optimizer.apply(e.params, e.grads, lr, self.global_step + 1, gscale)
             self.global_step += 1
             e._filters_dirty = True
+        self._update_ema()
+
+    def _update_ema(self):
+        """The step's one launch over the shadow arena, behind the final parameters on the current stream; t = the global step AFTER the update."""
+        if self.ema is None:
+            return
+        decay = ema_decay_at(self.ema_decay, self.global_step)
+        ops.ema_update(self.ema, self.engine.params, self.engine.n_params, float(np.float32(1.0 - decay)))
+
+    def reset_ema(self):
+        """Shadows := the current parameters (a device copy): a checkpoint without shadows, or a transfer, was restored."""
+        if self.ema is not None:
+            self.ema.copy_(self.engine.params)
 
     def gather_optimizer_state(self):
         """With optimizer sharding every rank holds valid optimizer slots for its own shards only: all-gathers them (collective: every rank

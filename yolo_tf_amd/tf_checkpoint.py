@@ -291,24 +291,52 @@ def checkpoint_step(prefix):
     return int(m.group(1)) if m else -1
 
 
-def restore(prefix, session=None, engine=None, exclude=None, variables_only=False):
+EMA_SUFFIX = '/ExponentialMovingAverage'      # tf.train.ExponentialMovingAverage.average_name(var) = <var>/ExponentialMovingAverage
+
+
+def restore(prefix, session=None, engine=None, exclude=None, variables_only=False, ema=False):
     """Variables of a TF checkpoint into the engine by name (``slim.assign_from_checkpoint_fn(model_path, tf.global_variables())``,
     detect.py:104-106): every graph variable found in the file is assigned; ``global_step`` and Adam's ``<var>/Adam``,
     ``<var>/Adam_1`` slots go into a TrainSession when one is given.  ``variables_only`` (the reference's ``-t ckpt -e scope...``
     transfer, train.py:114,130-136): no optimizer slots, and ``global_step`` is taken unless ``exclude`` names it -- as
     slim.get_variables_to_restore(exclude=...) does, so exponential_decay continues from the donor's step (checkpoint.restore
-    behaves the same).  Returns global_step (0 when absent)."""
+    behaves the same).  Returns global_step (0 when absent).
+
+    ``<var>/ExponentialMovingAverage`` tensors (written when the session keeps the weight average, [mi355x] ema_decay) go into such a session's
+    shadows on a full resume; without them, or on a transfer, the shadows are set to the restored parameters and one warning is logged.
+    ``ema=True`` (the ``engine=`` form) assigns the shadow values to the trainable variables instead of the raw ones; a file without shadows
+    raises SystemExit."""
     engine = engine if engine is not None else session.engine
     index = read_index(prefix)
     index.pop('', None)
     wanted = [v.name for v in engine.graph.variables.values() if v.name in index and not (exclude and any(v.name.startswith(s) for s in exclude))]
     extra = ['global_step'] if 'global_step' in index else []
+    trainable = set(v.name for v in engine.graph.trainable())
+    shadows = [n + EMA_SUFFIX for n in wanted if n in trainable and n + EMA_SUFFIX in index]
+    if ema:
+        if not shadows:
+            from .checkpoint import no_shadows
+            raise no_shadows(prefix)
+        extra = extra + shadows
+    keeps_ema = session is not None and getattr(session, 'ema', None) is not None
+    if keeps_ema and not variables_only:
+        extra = extra + shadows
     slots = []
     if session is not None and session.optimizer.name == 'adam' and not variables_only:
         slots = [n + sfx for n in wanted for sfx in ('/Adam', '/Adam_1') if n + sfx in index]
     values = read(prefix, set(wanted + extra + slots))
-    engine.set_variables({k: values[k] for k in wanted}, strict=False)
+    engine.set_variables({k: values[k + EMA_SUFFIX] if ema and k + EMA_SUFFIX in values else values[k] for k in wanted}, strict=False)
     step = int(values['global_step']) if 'global_step' in values else 0
+    if keeps_ema:
+        import logging
+        import torch
+        session.reset_ema()         # every shadow the file does not bring starts at its (restored) variable
+        if variables_only or not shadows:
+            logging.warning('%s: %s -- the moving averages of the weights start at the restored parameters', prefix,
+                            'a transfer' if variables_only else 'no moving averages in the file')
+        else:
+            for n in shadows:
+                session.ema_var[n[:-len(EMA_SUFFIX)]].copy_(torch.from_numpy(np.ascontiguousarray(values[n], np.float32).reshape(-1)))
     if session is not None:
         if not (variables_only and exclude and any('global_step'.startswith(s) for s in exclude)):
             session.global_step = step
@@ -340,6 +368,11 @@ def save(logdir, session, step=None, keep=5):
             for v in e.graph.trainable():
                 o, sz = e.param_offsets[v.name]
                 tensors[v.name + sfx] = host[o:o + sz].reshape(v.shape)
+    if getattr(session, 'ema', None) is not None:       # the weight average ([mi355x] ema_decay): tf.train.ExponentialMovingAverage's shadow variables
+        host = session.ema.cpu().numpy()
+        for v in e.graph.trainable():
+            o, sz = e.param_offsets[v.name]
+            tensors[v.name + EMA_SUFFIX] = host[o:o + sz].reshape(v.shape)
     prefix = os.path.join(logdir, 'model.ckpt-%d' % step)
     write(prefix, tensors)
     import glob
