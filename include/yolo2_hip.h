@@ -801,6 +801,32 @@ typedef struct yolo2_absmax_job {
     int slot;
 } yolo2_absmax_job;
 int yolo2_absmax(const yolo2_absmax_job *jobs, int njobs, unsigned *out, void *stream);
+/* Histograms of |x| of a list of tensors in one launch: the second calibration pass, after yolo2_absmax has fixed the ranges (the
+ * percentile, MSE and entropy thresholds of yolo_tf_amd/quant.py are chosen from them on the host).  Specification: tests/calib_ref.py.
+ * jobs: DEVICE table; job j reads its tensor as a yolo2_absmax job does and adds into record `slot` of out, YOLO2_CALIB_WORDS u64 words:
+ * YOLO2_CALIB_BINS equal bins over [0, limit], then the number of non-finite values, then the number of values above `limit`.  Several jobs
+ * may share a slot (a scale class: same limit, same inv_width).  The rule, for every element:
+ *   a = |float(x)|
+ *   a is NaN or inf: word[BINS] += 1, nothing else
+ *   t = a * inv_width                          one f32 multiply, one rounding; inv_width = float32(2048) / limit, computed by the HOST
+ *   b = (t >= 2048.f) ? 2047 : (int)t          compare before converting (t may be +inf)
+ *   word[b] += 1
+ *   a > limit: word[BINS + 1] += 1             the value was clamped into the last bin
+ * Everything behind the one multiply is integer, so a record is exact, independent of the order of the elements and identical run to run.
+ * The caller zeroes `out` once; successive calls (batches) keep accumulating.  limit and inv_width must be finite and > 0; a job that is not
+ * well formed (that, rows <= 0, c <= 0, ld < c, rows * ld > 2^40, slot < 0, an unknown dtype) counts nothing.  `base` needs the alignment
+ * of its element only (16-byte loads are used where base, c and ld allow).  NULL jobs / out or njobs outside 1 .. 65535 is YOLO2_E_ARG
+ * before any launch.  No workspace, no library-owned state, one launch. */
+#define YOLO2_CALIB_BINS  2048
+#define YOLO2_CALIB_WORDS (YOLO2_CALIB_BINS + 2)      /* u64 words per record */
+typedef struct yolo2_calib_job {
+    const void *base;
+    long long rows;
+    int c, ld, dtype;
+    int slot;
+    float limit, inv_width;
+} yolo2_calib_job;
+int yolo2_calib_histogram(const yolo2_calib_job *jobs, int njobs, unsigned long long *out, void *stream);
 /* Q[r*ldq + j] = quantise(X[r*ldx + j]) for r < rows, j < c (X: f32 / bf16) */
 int yolo2_quantize(const void *X, int ldx, void *Q, int ldq, long rows, int c, float inv_s, int dtype, void *stream);
 /* 2x2 SAME max pool on int8 bytes, stride 2 (output ceil(H/2) x ceil(W/2)) or stride 1 (output H x W); the window is clipped at the

@@ -3,6 +3,9 @@ tensor the int8 network stores, and writes the per-tensor scales next to the che
 
     python quantize.py -c config.ini config/yolo2/darknet-20.ini -p train --batches 8 -b 32 [--data synthetic|file.npz|cache] -o calibration.npz
 
+--method percentile | mse | entropy clips instead of taking the abs-max: a second pass over the same batches fills one histogram of |x| per
+scale class, the method picks a threshold from it, and one line per class says what it did (--percentile P: default 99.99).
+
 Afterwards `detect.py --dtype int8` and `eval.py --dtype int8` run the quantised network (--calibration FILE, default: the logdir's file).
 """
 import argparse
@@ -37,12 +40,22 @@ def main():
     images, objects = load_data(args, config, len(builder.names))[:2]
     m = sess.model
     data = evaluate.EvalData(images, objects, args.batch_size, builder.width, builder.height, m.cell_width, m.cell_height)
-    cal = quant.Calibrator(sess)
+    cal = quant.Calibrator(sess, method=args.method, percentile=args.percentile)
     for batch, _, _, _ in data:
         if cal.batches >= args.batches:
             break
         cal.observe(batch, PREPROCESS[args.preprocess])
+    if args.method != 'absmax':
+        for batch, _, _, _ in data:
+            if cal.hist_batches >= cal.batches:
+                break
+            cal.observe_histogram(batch, PREPROCESS[args.preprocess])
     calibration = cal.finish()
+    if args.method != 'absmax':
+        for r in cal.report:
+            print('%s: abs-max %.6g, %s threshold %.6g (%.4f of it), %.4f %% of the values clipped, SQNR estimate %.2f dB (abs-max: %.2f dB)' % (
+                ' '.join(r['members']), r['amax'], args.method, r['threshold'], r['threshold'] / r['amax'], 100 * r['clipped'], r['sqnr_db'],
+                r['sqnr_db_absmax']))
     out = os.path.expanduser(os.path.expandvars(args.output)) if args.output else os.path.join(logdir, quant.CALIBRATION_FILE)
     calibration.save(out)
     print('global_step=%d: %d batches of %d images, %d tensors in %d scale classes -> %s' % (
@@ -57,6 +70,9 @@ def make_args(argv=None):
     parser.add_argument('--data', default='cache', help="'cache' (the reference's TFRecord cache), 'synthetic' or a .npz file with raw objects")
     parser.add_argument('-b', '--batch_size', type=int, default=32)
     parser.add_argument('--batches', type=int, default=8, help='number of calibration batches')
+    parser.add_argument('--method', default='absmax', choices=['absmax', 'percentile', 'mse', 'entropy'],
+                        help='how a scale class gets its range: its abs-max, or a clipping threshold chosen from a histogram (a second pass over the batches)')
+    parser.add_argument('--percentile', type=float, default=99.99, help='--method percentile: the share of the values, in percent, the range keeps')
     parser.add_argument('--preprocess', default='std', choices=sorted(PREPROCESS), help='the preprocess function detection will use')
     parser.add_argument('-o', '--output', default=None, help='calibration file (default: calibration.npz in the logdir, beside the checkpoint)')
     parser.add_argument('--images', type=int, default=None, help='--data synthetic: number of images (default: batches * batch size)')

@@ -114,6 +114,7 @@ SIGNATURES = {
     'yolo2_image_summary': [_p, _i, _i, _p, ctypes.c_size_t, _p, ctypes.c_size_t, _p],
     'yolo2_conv2d_i8': [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, _p],
     'yolo2_absmax': [_p, _i, _p, _p],
+    'yolo2_calib_histogram': [_p, _i, _p, _p],
     'yolo2_quantize': [_p, _i, _p, _i, _l, _i, _f, _i, _p],
     'yolo2_maxpool_i8': [_p, _i, _p, _i, _i, _i, _i, _i, _i, _p],
     'yolo2_reorg_i8': [_p, _p, _i, _i, _i, _i, _i, _p],
@@ -192,6 +193,15 @@ class ImageJob(ctypes.Structure):
 class AbsmaxJob(ctypes.Structure):
     """yolo2_absmax_job of include/yolo2_hip.h"""
     _fields_ = [('base', ctypes.c_void_p), ('rows', ctypes.c_longlong), ('c', _i), ('ld', _i), ('dtype', _i), ('slot', _i)]
+
+
+CALIB_BINS = 2048                  # YOLO2_CALIB_BINS
+CALIB_WORDS = CALIB_BINS + 2       # YOLO2_CALIB_WORDS
+
+
+class CalibJob(ctypes.Structure):
+    """yolo2_calib_job of include/yolo2_hip.h"""
+    _fields_ = [('base', ctypes.c_void_p), ('rows', ctypes.c_longlong), ('c', _i), ('ld', _i), ('dtype', _i), ('slot', _i), ('limit', _f), ('inv_width', _f)]
 
 
 class FilterDesc(ctypes.Structure):

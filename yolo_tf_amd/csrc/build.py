@@ -36,6 +36,7 @@ SOURCES = {
     'image_summary.hip': ['-ffp-contract=off'],
     'conv_i8.hip': ['-ffp-contract=off'],
     'quant.hip': ['-ffp-contract=off'],
+    'calib.hip': ['-ffp-contract=off'],
     'ema.hip': ['-ffp-contract=off'],
 }
 COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics', '-Wno-unused-result']

@@ -790,6 +790,49 @@ class AbsmaxJobs(object):
         return np.ascontiguousarray(words[:, 0]).view(np.float32).copy(), words[:, 1].astype(np.int64)
 
 
+CALIB_BINS, CALIB_WORDS = _lib.CALIB_BINS, _lib.CALIB_WORDS
+
+
+class CalibHistogramJobs(object):
+    """Device job table of yolo2_calib_histogram over a fixed list of tensors, with its running records.
+
+    ``jobs``: [(tensor, rows, c, ld, slot, limit)] -- as AbsmaxJobs, plus the range [0, limit] of the record's CALIB_BINS bins (finite, > 0;
+    jobs that share a slot carry the same limit).  ``launch()`` adds the tensors' current contents to the records (``out``: int64
+    [nslots, CALIB_WORDS] on the device, holding the kernel's u64 words); ``result()`` -> (histograms int64 [nslots, CALIB_BINS], non-finite
+    counts int64 [nslots], counts of values above the limit int64 [nslots])."""
+
+    def __init__(self, jobs, nslots, device=None):
+        from ._lib import CalibJob
+        assert len(jobs) > 0
+        self.tensors = [j[0] for j in jobs]
+        self.device = device if device is not None else self.tensors[0].device
+        arr = (CalibJob * len(jobs))()
+        self.limits = {}
+        for d, (t, rows, c, ld, slot, limit) in zip(arr, jobs):
+            rows, c, ld, slot, limit = int(rows), int(c), int(ld), int(slot), np.float32(limit)
+            assert t.is_cuda and t.is_contiguous() and 0 < c <= ld and rows > 0 and 0 <= slot < nslots, (rows, c, ld, slot)
+            assert (rows - 1) * ld + c <= t.numel(), 'histogram job of %d elements on a tensor of %d' % ((rows - 1) * ld + c, t.numel())
+            assert rows * ld <= 2 ** 40, (rows, ld)
+            assert np.isfinite(limit) and limit > 0, 'histogram limit %r' % (limit,)
+            with np.errstate(all='ignore'):
+                inv_width = np.float32(CALIB_BINS) / limit             # f32: the kernel's one multiply uses exactly this value
+            assert np.isfinite(inv_width), 'histogram limit %r is too small' % (limit,)
+            assert self.limits.setdefault(slot, limit) == limit, 'the jobs of slot %d disagree on the limit' % slot
+            d.base, d.rows, d.c, d.ld, d.dtype, d.slot, d.limit, d.inv_width = t.data_ptr(), rows, c, ld, dtype_code(t.dtype), slot, limit, inv_width
+        self.n, self.nslots = len(jobs), int(nslots)
+        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
+        self.out = torch.zeros(self.nslots, CALIB_WORDS, dtype=torch.int64, device=self.device)
+
+    def launch(self):
+        call('yolo2_calib_histogram', ptr(self.table), self.n, ptr(self.out), _stream())
+
+    def result(self):
+        words = self.out.cpu().numpy().view(np.uint64)
+        assert int(words.max()) < 2 ** 63
+        words = words.astype(np.int64)
+        return words[:, :CALIB_BINS].copy(), words[:, CALIB_BINS].copy(), words[:, CALIB_BINS + 1].copy()
+
+
 def quantize(X, ldx, Q, ldq, rows, c, inv_s):
     call('yolo2_quantize', ptr(X), ldx, ptr(Q), ldq, rows, c, float(inv_s), dtype_code(X.dtype), _stream())
 

@@ -8,6 +8,9 @@ on yolo2_conv2d_i8.  The head writes bf16 logits, so decode, NMS and the evaluat
 Symmetric int8 in -127 .. 127: q = clip(rint(x * inv_s), -127, 127), inv_s = float32(1) / s.  Activations: one scale per tensor,
 s = absmax / 127; tensors connected by a pool, reorg or concat share the max of their abs-max (those ops then move bytes).  Weights: one
 scale per output channel over the BN-folded f32 filter, quantised here on the host once per set of variables.
+
+Calibration methods: 'absmax' as above, or a clipping threshold T in the abs-max's place (s = T / 127), chosen per scale class from a
+2048-bin histogram of |x| that a second pass over the batches fills on the device: 'percentile', 'mse', 'entropy' (threshold_* below).
 """
 import logging
 import os
@@ -115,24 +118,152 @@ class QuantPlan(object):
         return [t.name for t in self.tensors]
 
 
-class Calibration(object):
-    """Names and f32 scales of the int8 tensors of one network (tensors of a scale class carry the same value)."""
+METHODS = ('absmax', 'percentile', 'mse', 'entropy')
+BINS = 2048                 # YOLO2_CALIB_BINS: bins of a calibration histogram over [0, abs-max of the scale class]
+FIRST_CANDIDATE = 128       # the smallest clipping threshold 'mse' and 'entropy' consider, in bins (one sixteenth of the abs-max)
 
-    def __init__(self, scales):
+
+# ---- clipping thresholds from a histogram of |x| (host, f64; specification: tests/calib_ref.py) ---------------------------------------------
+# h: counts of BINS equal bins over [0, limit], values above limit in the last one; w = limit / BINS.  Each rule returns the threshold T that
+# takes the abs-max's place in scale_of; candidates are bin edges T_i = i * w, the smallest i wins ties.
+
+def threshold_percentile(h, limit, p=99.99):
+    """The upper edge of the first bin at which the cumulative count reaches ceil(total * p / 100); p = 100: the limit itself."""
+    h = np.asarray(h, np.int64)
+    total = int(h.sum())
+    if p >= 100 or total == 0:
+        return float(limit)
+    need = int(np.ceil(total * float(p) / 100.0))
+    b = int(np.searchsorted(np.cumsum(h), need, side='left'))
+    return (b + 1) * (float(limit) / BINS)
+
+
+def _mse_objective(h, limit):
+    """sum over bins of h_b (x_b - q_b)^2 for every candidate i = FIRST_CANDIDATE .. BINS: the project's quantiser, s = T_i / 127, applied to
+    the bin centres x_b = (b + 0.5) w.  -> f64 [BINS - FIRST_CANDIDATE + 1]"""
+    w = float(limit) / BINS
+    x = (np.arange(BINS, dtype=np.float64) + 0.5) * w
+    s = (np.arange(FIRST_CANDIDATE, BINS + 1, dtype=np.float64) * w / 127.0)[:, None]
+    q = np.minimum(np.rint(x[None, :] / s), 127.0) * s
+    return ((x[None, :] - q) ** 2) @ np.asarray(h, np.float64)
+
+
+def threshold_mse(h, limit):
+    if int(np.asarray(h, np.int64).sum()) == 0:
+        return float(limit)
+    return (FIRST_CANDIDATE + int(np.argmin(_mse_objective(h, limit)))) * (float(limit) / BINS)
+
+
+def _kl(h, i):
+    """KL(P || Q) of candidate i, or None when Q is 0 somewhere P is not.  P: the first i bins with everything above folded into bin i - 1.
+    Q: those i bins (without the folded tail) merged into 128 groups by b * 128 // i, each group's sum spread evenly over its non-zero bins."""
+    head = h[:i]
+    P = head.copy()
+    P[i - 1] += h[i:].sum()
+    g = np.arange(i) * 128 // i
+    nz = head > 0
+    gsum = np.bincount(g, weights=head, minlength=128)
+    gnz = np.bincount(g, weights=nz, minlength=128)
+    Q = np.where(nz, gsum[g] / np.maximum(gnz[g], 1.0), 0.0)
+    pos = P > 0
+    if (Q[pos] == 0).any():
+        return None
+    P = P / P.sum()
+    Q = Q / Q.sum()
+    return float(np.sum(P[pos] * np.log(P[pos] / Q[pos])))
+
+
+def threshold_entropy(h, limit):
+    """The usual KL calibrator: the candidate whose 128-level picture of the clipped distribution loses the least information."""
+    h = np.asarray(h, np.float64)
+    best, best_i = None, BINS
+    if h.sum() > 0:
+        for i in range(FIRST_CANDIDATE, BINS + 1):
+            kl = _kl(h, i)
+            if kl is not None and (best is None or kl < best):
+                best, best_i = kl, i
+    return best_i * (float(limit) / BINS)
+
+
+def choose_threshold(h, limit, method, percentile=99.99):
+    if method == 'percentile':
+        return threshold_percentile(h, limit, percentile)
+    if method == 'mse':
+        return threshold_mse(h, limit)
+    if method == 'entropy':
+        return threshold_entropy(h, limit)
+    raise ValueError('calibration method %r: expected one of %s' % (method, ', '.join(METHODS)))
+
+
+def histogram_sqnr_db(h, limit, T):
+    """The histogram's estimate of the signal-to-quantisation-noise ratio under threshold T, in dB: bin centres through the quantiser."""
+    w = float(limit) / BINS
+    x = (np.arange(BINS, dtype=np.float64) + 0.5) * w
+    s = float(T) / 127.0
+    q = np.minimum(np.rint(x / s), 127.0) * s
+    h = np.asarray(h, np.float64)
+    noise, signal = float(np.sum(h * (x - q) ** 2)), float(np.sum(h * x * x))
+    return 10.0 * np.log10(signal / noise) if noise > 0 and signal > 0 else float('inf')
+
+
+class Calibration(object):
+    """Names and f32 scales of the int8 tensors of one network (tensors of a scale class carry the same value).  A calibration made with a
+    clipping method also records the method, every tensor's class abs-max and the threshold chosen for it; the int8 engine reads the scales."""
+
+    def __init__(self, scales, method='absmax', amax=None, thresholds=None):
         self.scales = {str(k): F32(v) for k, v in scales.items()}
+        self.method = str(method)
+        self.amax = None if amax is None else {str(k): F32(v) for k, v in amax.items()}
+        self.thresholds = None if thresholds is None else {str(k): F32(v) for k, v in thresholds.items()}
 
     def save(self, path):
         names = sorted(self.scales)
+        arrays = dict(names=np.array(names), scales=np.array([self.scales[n] for n in names], F32))
+        if self.method != 'absmax':
+            arrays.update(method=np.array(self.method), amax=np.array([self.amax[n] for n in names], F32),
+                          thresholds=np.array([self.thresholds[n] for n in names], F32))
         with open(path, 'wb') as f:
-            np.savez(f, names=np.array(names), scales=np.array([self.scales[n] for n in names], F32))
+            np.savez(f, **arrays)
 
     @classmethod
     def load(cls, path):
         z = np.load(path, allow_pickle=False)
-        return cls(dict(zip((str(n) for n in z['names']), z['scales'].astype(F32))))
+        names = [str(n) for n in z['names']]
+        if 'method' not in z.files:
+            return cls(dict(zip(names, z['scales'].astype(F32))))
+        return cls(dict(zip(names, z['scales'].astype(F32))), method=str(z['method']), amax=dict(zip(names, z['amax'].astype(F32))),
+                   thresholds=dict(zip(names, z['thresholds'].astype(F32))))
 
     def __eq__(self, other):
-        return isinstance(other, Calibration) and self.scales == other.scales
+        return (isinstance(other, Calibration) and self.scales == other.scales and self.method == other.method and self.amax == other.amax
+                and self.thresholds == other.thresholds)
+
+
+def calibration_from_absmax(classes, amax):
+    """classes: [[tensor name]]; amax: {tensor name: abs-max} -> Calibration with s = (the largest abs-max of the class) / 127."""
+    scales = {}
+    for cls in classes:
+        s = scale_of(max(F32(amax[n]) for n in cls))
+        for n in cls:
+            scales[n] = s
+    return Calibration(scales)
+
+
+def calibration_from_histograms(classes, limits, hists, method, percentile=99.99):
+    """classes: [[tensor name]]; limits[k] / hists[k]: the abs-max of class k and the histogram of |x| over [0, limits[k]] its members share.
+    -> (Calibration, one report dict per class that has a histogram).  A class whose abs-max is 0 or not finite keeps s = 1."""
+    scales, amax, thresholds, report = {}, {}, {}, []
+    for cls, limit, h in zip(classes, limits, hists):
+        limit = T = F32(limit)
+        h = np.asarray(h, np.int64)
+        if np.isfinite(limit) and limit > 0 and h.sum() > 0:
+            T = F32(choose_threshold(h, limit, method, percentile))
+            first = int(round(float(T) / (float(limit) / BINS)))
+            report.append({'members': list(cls), 'amax': float(limit), 'threshold': float(T), 'clipped': float(h[first:].sum()) / float(h.sum()),
+                           'sqnr_db': histogram_sqnr_db(h, limit, T), 'sqnr_db_absmax': histogram_sqnr_db(h, limit, limit)})
+        for n in cls:
+            scales[n], amax[n], thresholds[n] = scale_of(T), limit, T
+    return Calibration(scales, method=method, amax=amax, thresholds=thresholds), report
 
 
 class Calibrator(object):
@@ -140,9 +271,19 @@ class Calibrator(object):
 
     The session's own engine never stores the activation in front of a fused max pool, and the abs-max of a scale class is taken over the
     un-pooled tensor too, so the calibrator drives an engine of its own with the pools un-fused (the image layer's excepted: its raw output
-    is not an int8 tensor).  ``engine`` is that engine: after ``observe`` its activations are the ones the abs-max was taken of."""
+    is not an int8 tensor).  ``engine`` is that engine: after ``observe`` its activations are the ones the abs-max was taken of.
 
-    def __init__(self, detect_session):
+    ``method`` 'absmax' stops there.  'percentile', 'mse' and 'entropy' need a second pass over the same batches, ``observe_histogram``: its
+    first call freezes each scale class's abs-max as the range of one 2048-bin histogram of |x| shared by the class's tensors
+    (yolo2_calib_histogram, one launch per batch), and ``finish`` puts the threshold the method picks from it in the abs-max's place."""
+
+    def __init__(self, detect_session, method='absmax', percentile=99.99):
+        if method not in METHODS:
+            raise ValueError('calibration method %r: expected one of %s' % (method, ', '.join(METHODS)))
+        if not 0 < float(percentile) <= 100:
+            raise ValueError('percentile %r is not in (0, 100]' % (percentile,))
+        self.method, self.percentile = method, float(percentile)
+        self.hist_jobs, self.hist_batches, self.limits = None, 0, None
         src = detect_session.engine
         if not isinstance(src, Engine):
             raise TypeError('calibration runs on a bf16 / f32 DetectSession')
@@ -159,7 +300,9 @@ class Calibrator(object):
         self.batches = 0
 
     def observe(self, images, preprocess_mode=0):
-        """images: device f32 [B,H,W,3] as for DetectSession.run."""
+        """Pass 1.  images: device f32 [B,H,W,3] as for DetectSession.run."""
+        if self.limits is not None:
+            raise RuntimeError('the histogram ranges are frozen: observe() cannot follow observe_histogram()')
         self.engine.set_images(images, preprocess_mode)
         self.engine.forward()
         self.jobs.launch()
@@ -170,24 +313,71 @@ class Calibrator(object):
         amax, bad = self.jobs.result()
         return {t.name: F32(a) for t, a in zip(self.plan.tensors, amax)}, int(bad.sum())
 
+    def class_absmax(self):
+        """-> [abs-max f32 of each scale class, in the order of plan.classes]"""
+        amax, _ = self.absmax()
+        return [F32(max(amax[t.name] for t in cls)) for cls in self.plan.classes]
+
+    def observe_histogram(self, images, preprocess_mode=0):
+        """Pass 2 (the clipping methods): the same batches again, after every observe().  The first call freezes the ranges."""
+        if self.method == 'absmax':
+            raise RuntimeError("method 'absmax' takes no histogram")
+        if self.limits is None:
+            assert self.batches > 0, 'no calibration batch was observed'
+            self.limits = self.class_absmax()
+            e, jobs = self.engine, []
+            for k, (cls, limit) in enumerate(zip(self.plan.classes, self.limits)):
+                if not np.isfinite(limit) or limit == 0:      # nothing to bin: the class keeps s = 1
+                    continue
+                for t in cls:
+                    buf, ld = e.act[t]
+                    jobs.append((buf, e.B * t.h * t.w, t.c, ld, k, limit))
+            if jobs:
+                self.hist_jobs = ops.CalibHistogramJobs(jobs, len(self.plan.classes), device=e.device)
+        self.engine.set_images(images, preprocess_mode)
+        self.engine.forward()
+        if self.hist_jobs is not None:
+            self.hist_jobs.launch()
+        self.hist_batches += 1
+
+    def histograms(self):
+        """-> (counts int64 [classes, 2048], values above the frozen range int64 [classes]); zeros for a class without a job"""
+        n = len(self.plan.classes)
+        if self.hist_jobs is None:
+            return np.zeros((n, BINS), np.int64), np.zeros(n, np.int64)
+        h, _, clamped = self.hist_jobs.result()
+        return h, clamped
+
     def finish(self):
         assert self.batches > 0, 'no calibration batch was observed'
         amax, bad = self.absmax()
         if bad:
             logging.warning('calibration: %d non-finite activation values were ignored', bad)
-        scales = {}
-        for cls in self.plan.classes:
-            s = scale_of(max(amax[t.name] for t in cls))
-            for t in cls:
-                scales[t.name] = s
-        return Calibration(scales)
+        classes = [[t.name for t in cls] for cls in self.plan.classes]
+        if self.method == 'absmax':
+            return calibration_from_absmax(classes, amax)
+        if self.hist_batches == 0:
+            raise RuntimeError("calibration method '%s' needs a second pass over the calibration batches: call observe_histogram() for each of "
+                               'them after the last observe()' % self.method)
+        h, clamped = self.histograms()
+        if clamped.sum():
+            logging.warning('calibration: %d values lay above the abs-max of the first pass and were counted in the last bin (the second pass '
+                            'saw other data than the first)', int(clamped.sum()))
+        calibration, self.report = calibration_from_histograms(classes, self.limits, h, self.method, self.percentile)
+        return calibration
 
 
-def calibrate(detect_session, batches, preprocess_mode=0):
-    """batches: iterable of device f32 image tensors [B,H,W,3] -> Calibration."""
-    c = Calibrator(detect_session)
+def calibrate(detect_session, batches, preprocess_mode=0, method='absmax', percentile=99.99):
+    """batches: iterable of device f32 image tensors [B,H,W,3] -> Calibration.  The clipping methods go over the batches twice (a one-shot
+    iterator is materialised into a list first)."""
+    c = Calibrator(detect_session, method, percentile)
+    if method != 'absmax' and iter(batches) is batches:
+        batches = list(batches)
     for images in batches:
         c.observe(images, preprocess_mode)
+    if method != 'absmax':
+        for images in batches:
+            c.observe_histogram(images, preprocess_mode)
     return c.finish()
 
 
