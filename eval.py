@@ -12,6 +12,8 @@ seeded generator.  Images are resized by the device's TF-style bilinear kernel, 
 ``--protocol coco`` prints COCO's twelve numbers (AP@[.5:.95], AP50, AP75, AP by area, AR by detection limit and by area) instead.  A
 .npz file may bring ``objects_crowd`` and ``objects_area``; the reference's cache has no crowd flag (utils/data/cache.py:127 reads
 crowd annotations as ordinary boxes), so with ``--data cache`` every box counts and its area is its box area.
+``--sizes SPEC`` evaluates the one checkpoint at several input sizes (YOLO9000, table 3): restored once, the dataset uploaded once, one table
+under a ``size WxH`` line per size, a closing table (size, the two mean APs, milliseconds per batch by HIP events), ``by_size`` in the JSON.
 Import-safe."""
 import argparse
 import configparser
@@ -56,7 +58,22 @@ def main():
     if dtype == 'int8':       # post-training quantised inference: the scales quantize.py measured for this checkpoint
         from yolo_tf_amd import quant
         calibration = quant.calibration_path(logdir, args.calibration)
-    sess = DetectSession(builder, args.batch_size, dtype=dtype, calibration=calibration)
+    sizes = None
+    if args.sizes is not None:
+        # one set of weights at several input sizes (YOLO9000, table 3): restored once, evaluated once per size
+        from yolo_tf_amd import multiscale
+        if model == 'yolo':
+            raise ValueError('--sizes %r: the fully connected head of the YOLO (v1) family fixes the input size' % args.sizes)
+        try:
+            sizes = multiscale.parse_sizes(args.sizes, *utils.get_downsampling(config))
+        except ValueError as e:
+            raise ValueError('--sizes %r: %s' % (args.sizes, e))
+        if not sizes:
+            raise ValueError('--sizes %r names no size' % args.sizes)
+        multiscale.check_nested(sorted(set(sizes) | {(builder.width, builder.height)}), '--sizes %r' % args.sizes)
+        if dtype == 'int8':
+            raise ValueError('--sizes with --dtype int8: quantised inference binds one input size; run eval.py once per size')
+    sess = DetectSession(builder, args.batch_size, dtype=dtype, calibration=calibration, sizes=sizes)
     model_path = checkpoint.latest_checkpoint(logdir)
     tf_path = None if model_path else tf_checkpoint.latest_checkpoint(logdir)
     if model_path is None and tf_path is None:
@@ -67,31 +84,65 @@ def main():
     images, objects, difficult, crowd, area = load_data(args, config, len(builder.names))
     m = sess.model
     data = evaluate.EvalData(images, objects, args.batch_size, builder.width, builder.height, m.cell_width, m.cell_height, difficult=difficult,
-                             crowd=crowd, area=area)
-    result = evaluate.evaluate(builder, sess, data, mode=args.mode, threshold=args.threshold, threshold_iou=args.threshold_iou, iou=args.iou,
-                               preprocess_mode=PREPROCESS[args.preprocess], max_records=args.max_records, protocol=args.protocol)
+                             crowd=crowd, area=area, input_sizes=sizes)
     extra = dict(names=list(builder.names), images=len(images), checkpoint=model_path or tf_path, global_step=int(step), calibration=calibration, ema=bool(args.ema),
                  config={k: getattr(args, k) for k in ('config', 'profile', 'data', 'batch_size', 'threshold', 'threshold_iou', 'iou', 'mode', 'protocol',
                                                        'preprocess', 'dtype', 'limit', 'images', 'seed')})
+
+    def run(on_batch=None):
+        return evaluate.evaluate(builder, sess, data, mode=args.mode, threshold=args.threshold, threshold_iou=args.threshold_iou, iou=args.iou,
+                                 preprocess_mode=PREPROCESS[args.preprocess], max_records=args.max_records, protocol=args.protocol, on_batch=on_batch)
+    if sizes is None:
+        result = run()
+        out = report(args, builder, result)
+        if args.json:
+            write_json(args.json, dict(out, **extra))
+        return result
+    import torch
+    by_size, ms, results = {}, {}, {}
+    for w, h in sizes:
+        key = '%dx%d' % (w, h)
+        sess.set_size(w, h)
+        data.set_size(w, h)
+        # HIP events around the batches (resize, forward, decode, NMS, matching), not around the final sort and download; the first
+        # batch at a size builds that size's plans, which is part of the figure
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        result = run(on_batch=lambda *a: end.record())
+        end.synchronize()
+        ms[key] = start.elapsed_time(end) / len(data)
+        print('size ' + key)
+        by_size[key] = report(args, builder, result)
+        results[key] = result
+    coco = args.protocol == 'coco'
+    print(('%-10s %8s %8s %12s' % ('size', 'AP', 'AP50', 'ms/batch')) if coco else ('%-10s %8s %8s %12s' % ('size', 'mAP07', 'mAP12', 'ms/batch')))
+    for key, result in results.items():
+        a, b = (result['stats'][0], result['stats'][1]) if coco else (result['mAP07'], result['mAP12'])
+        print('%-10s %8.4f %8.4f %12.3f' % (key, a, b, ms[key]))
+    if args.json:
+        write_json(args.json, dict(extra, sizes=list(by_size), by_size=by_size, ms_per_batch=ms))
+    return results
+
+
+def report(args, builder, result):
+    """Prints one evaluation's table and returns what --json writes of it."""
+    from yolo_tf_amd import evaluate
     if args.protocol == 'coco':
         for name, v in zip(evaluate.COCO_STAT_NAMES, result['stats']):
             print('%s = %0.3f' % (name, v))
-        if args.json:
-            out = dict(extra, stats=result['stats'], stat_names=[n.strip() for n in evaluate.COCO_STAT_NAMES], detections=result['detections'],
-                       **{k: result[k].tolist() for k in ('ap', 'recall', 'npig')})
-            with open(os.path.expanduser(os.path.expandvars(args.json)), 'w') as f:
-                json.dump(out, f, indent=1)
-        return result
+        return dict(stats=result['stats'], stat_names=[n.strip() for n in evaluate.COCO_STAT_NAMES], detections=result['detections'],
+                    **{k: result[k].tolist() for k in ('ap', 'recall', 'npig')})
     print('%-16s %8s %8s %6s %6s %8s' % ('class', 'ap07', 'ap12', 'npos', 'tp', 'fp'))
     for i, name in enumerate(builder.names):
         print('%-16s %8.4f %8.4f %6d %6d %8d' % (name, result['ap07'][i], result['ap12'][i], result['npos'][i], result['tp'][i], result['fp'][i]))
     print('mAP07 %.4f' % result['mAP07'])
     print('mAP12 %.4f' % result['mAP12'])
-    if args.json:
-        out = dict(result, **extra)
-        with open(os.path.expanduser(os.path.expandvars(args.json)), 'w') as f:
-            json.dump(out, f, indent=1)          # (NaN of a class without ground truth is written as NaN, which Python's json reads back)
-    return result
+    return dict(result)
+
+
+def write_json(path, out):
+    with open(os.path.expanduser(os.path.expandvars(path)), 'w') as f:
+        json.dump(out, f, indent=1)          # (NaN of a class without ground truth is written as NaN, which Python's json reads back)
 
 
 def make_args(argv=None):
@@ -117,6 +168,8 @@ def make_args(argv=None):
     parser.add_argument('--max_records', type=int, default=None, help='capacity of the record buffer (default: the worst case of the mode)')
     parser.add_argument('--dtype', default=None, choices=['bf16', 'f32', 'int8'], help="'int8': post-training quantised inference (needs a calibration)")
     parser.add_argument('--calibration', default=None, help='--dtype int8: the file quantize.py wrote (default: calibration.npz in the logdir)')
+    parser.add_argument('--sizes', default=None, help="evaluate the one checkpoint at several input sizes: entries S, WxH or LO-HI (squares in steps of the "
+                        "network's stride) separated by spaces or commas, e.g. '320-608'; prints one table per size and a closing one, --json gets by_size")
     parser.add_argument('--ema', action='store_true', help='use the moving averages of the weights a run with [mi355x] ema_decay keeps in its checkpoints')
     parser.add_argument('--level', default='info', help='logging level')
     return parser.parse_args(argv)

@@ -13,7 +13,8 @@ TFRecord/JPEG input pipeline is out of the hot-path scope: batch
 objects_class [total], objects_coord [total,4] pixels, objects_first [N+1]); the latter goes through the on-device
 input pipeline (utils/augment.py: crop / resize / colour augmentation per config.ini [data_augmentation_*], labels
 built on the GPU) -- the counterpart of the reference's load_image_labels after JPEG decode.  ``--data cache`` reads the
-reference's own TFRecord cache (<cachedir>/<profile>.tfrecord for every ``-p`` profile, utils/tfrecord.py) into HBM."""
+reference's own TFRecord cache (<cachedir>/<profile>.tfrecord for every ``-p`` profile, utils/tfrecord.py) into HBM.
+``--multiscale SPEC`` / ``[mi355x] multiscale`` trains at a size drawn from a list every ``--multiscale_every`` steps (yolo_tf_amd/multiscale.py)."""
 import argparse
 import configparser
 import logging
@@ -25,7 +26,7 @@ import time
 import numpy as np
 import torch
 
-from yolo_tf_amd import checkpoint, tf_checkpoint, utils
+from yolo_tf_amd import checkpoint, multiscale, tf_checkpoint, utils
 from yolo_tf_amd.utils import events
 from yolo_tf_amd.parallel import agree, init_distributed, sync_replicas
 from yolo_tf_amd.session import TrainSession
@@ -33,7 +34,7 @@ from yolo_tf_amd.summary import HistogramSummaries, ImageSummaries
 from yolo_tf_amd.utils import data as udata
 
 
-def make_args():
+def make_args(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument('-c', '--config', nargs='+', default=['config.ini'], help='config file')
     parser.add_argument('-t', '--transfer', help='transferring model from a checkpoint file')
@@ -57,19 +58,28 @@ def make_args():
     parser.add_argument('--dtype', default=None, choices=['bf16', 'f32'], help='overrides [mi355x] dtype')
     parser.add_argument('--deterministic', action='store_true', help='bitwise reproducible training steps (also [mi355x] deterministic / YOLO2_DETERMINISTIC=1): '
                         'filter gradients summed through a workspace in a fixed order, no float atomics anywhere in the step')
+    parser.add_argument('--multiscale', default=None, help="overrides [mi355x] multiscale: input sizes drawn during training, entries S, WxH or LO-HI (squares in "
+                        "steps of the network's stride) separated by spaces or commas, e.g. '320-608'; '' turns it off")
+    parser.add_argument('--multiscale_every', default=None, type=int, help='overrides [mi355x] multiscale_every: steps a drawn size holds (default 10)')
     parser.add_argument('--ckpt_format', default='npz', choices=['npz', 'tf'], help="checkpoint container: 'npz' (every optimizer) or 'tf' (TensorFlow V2 bundle, as the reference's tf.train.Saver writes)")
-    return parser.parse_args()
+    return parser.parse_args(argv)
 
 
 class SyntheticData(object):
-    def __init__(self, batch, classes, width, height, cell_width, cell_height, seed):
+    """``session`` and ``downsampling`` (multi-scale): images and labels are made at the session's current size."""
+
+    def __init__(self, batch, classes, width, height, cell_width, cell_height, seed, session=None, downsampling=None):
         self.args = (batch, classes, cell_width, cell_height)
         self.gen = torch.Generator(device='cuda').manual_seed(seed)
         self.shape = (batch, height, width, 3)
         self.seed = seed
         self.i = 0
+        self.session, self.downsampling = session, downsampling
 
     def next(self):
+        if self.session is not None:
+            (w, h), (dw, dh) = self.session.size, self.downsampling
+            self.shape, self.args = (self.shape[0], h, w, 3), self.args[:2] + (w // dw, h // dh)
         images = torch.rand(*self.shape, device='cuda', generator=self.gen) * 255.0
         labels = udata.synthetic_batch(*self.args, seed=self.seed * 1000003 + self.i)
         self.i += 1
@@ -94,7 +104,7 @@ class NpzData(object):
 class DeviceAugmentedData(object):
     """Decoded images + raw boxes resident in HBM -> augmented batch and label tensors, all on the device."""
 
-    def __init__(self, z, batch, width, height, classes, cell_width, cell_height, config, seed, rank, world, session):
+    def __init__(self, z, batch, width, height, classes, cell_width, cell_height, config, seed, rank, world, session, sizes=None, downsampling=None):
         from yolo_tf_amd.utils.augment import DeviceInputPipeline
         if isinstance(z, tuple):          # (images, objects) already decoded, e.g. from the reference's TFRecord cache
             images, objects = z
@@ -103,14 +113,26 @@ class DeviceAugmentedData(object):
             first = z['objects_first']
             objects = [(z['objects_class'][first[i]:first[i + 1]], z['objects_coord'][first[i]:first[i + 1]]) for i in range(len(images))]
         self.pipe = DeviceInputPipeline(images, objects, batch, width, height, classes, cell_width, cell_height, config=config,
-                                        seed=seed, rank=rank, world=world)
+                                        seed=seed, rank=rank, world=world, sizes=sizes, downsampling=downsampling)
         self.session = session
 
     def next(self):
         return self.pipe.next(self.session), None          # labels were written into the session's buffers in place
 
 
+def multiscale_setting(args, config):
+    """[mi355x] multiscale / multiscale_every with the command line's overrides: None (absent or empty: nothing about the run changes) or
+    (sizes, every, added) of multiscale.configure.  Raises ValueError for what cannot train at several sizes, before anything is built."""
+    setting = multiscale.configure(config, args.multiscale, args.multiscale_every)
+    if setting is not None and args.data not in ('synthetic', 'cache') and 'objects_coord' not in np.load(args.data, allow_pickle=True).files:
+        raise ValueError('[mi355x] multiscale = %r: --data %s holds ready-made label tensors, which are laid out for one grid; multi-scale training '
+                         'needs raw objects (objects_class, objects_coord, objects_first), the dataset cache or synthetic data'
+                         % (multiscale.describe(setting[0]), args.data))
+    return setting
+
+
 def main():
+    setting = multiscale_setting(args, config)       # (a refusal comes before the process group and the device are touched)
     rank, local_rank, world = init_distributed()
     torch.cuda.set_device(local_rank)
     model = config.get('config', 'model')
@@ -131,8 +153,16 @@ def main():
     builder.create_objectives()
     dtype = args.dtype or (config.get('mi355x', 'dtype') if config.has_option('mi355x', 'dtype') else 'bf16')
     seed = args.seed if args.seed is not None else 0
+    sizes, schedule, downsampling = None, None, None
+    if setting is not None:
+        sizes, every, added = setting
+        downsampling = utils.get_downsampling(config)
+        schedule = multiscale.SizeSchedule(sizes, every, seed)
+        if added:
+            logging.warning('multiscale: the configured size %dx%d was not in the list and is added' % (width, height))
+        logging.warning('multiscale: sizes %s, a new draw every %d steps' % (multiscale.describe(sizes), every))
     session = TrainSession(builder, args.batch_size, dtype=dtype, optimizer=args.optimizer, learning_rate=args.learning_rate,
-                           gradient_clip=args.gradient_clip, config=config, seed=seed, world_size=world,
+                           gradient_clip=args.gradient_clip, config=config, seed=seed, world_size=world, sizes=sizes,
                            bucket_mb=config.getfloat('mi355x', 'bucket_mb') if config.has_option('mi355x', 'bucket_mb') else 64.0,
                            grad_dtype=config.get('mi355x', 'grad_dtype') if config.has_option('mi355x', 'grad_dtype') else 'f32',
                            sync_bn=config.getboolean('mi355x', 'sync_bn') if config.has_option('mi355x', 'sync_bn') else False,
@@ -172,7 +202,8 @@ def main():
     sync_replicas(session)
     logging.warning('global_step=%d, learning_rate=%g' % (session.global_step, session.lr_fn(session.global_step)))
     if args.data == 'synthetic':
-        data = SyntheticData(args.batch_size, len(builder.names), width, height, cell_width, cell_height, seed * world + rank + 1)
+        data = SyntheticData(args.batch_size, len(builder.names), width, height, cell_width, cell_height, seed * world + rank + 1,
+                             session=session if schedule is not None else None, downsampling=downsampling)
     elif args.data == 'cache':
         # the reference's own dataset cache: <cachedir>/<profile>.tfrecord written by its cache.py (train.py:98-100 there)
         from yolo_tf_amd.utils import tfrecord
@@ -180,10 +211,10 @@ def main():
         paths = [os.path.join(cachedir, profile + '.tfrecord') for profile in args.profile]
         logging.warning('loading ' + ', '.join(paths))
         data = DeviceAugmentedData(tfrecord.load_dataset(paths), args.batch_size, width, height, len(builder.names), cell_width, cell_height,
-                                   config, seed, rank, world, session)
+                                   config, seed, rank, world, session, sizes=sizes, downsampling=downsampling)
     elif 'objects_coord' in np.load(args.data, allow_pickle=True).files:
         data = DeviceAugmentedData(np.load(args.data, allow_pickle=True), args.batch_size, width, height, len(builder.names), cell_width, cell_height,
-                                   config, seed, rank, world, session)
+                                   config, seed, rank, world, session, sizes=sizes, downsampling=downsampling)
     else:
         data = NpzData(args.data, args.batch_size, seed, rank, world)
     # the reference's summary_writer (train.py:141-145): scalar events under <logdir>/<logname>
@@ -200,6 +231,7 @@ def main():
     sync_every = 1 if world == 1 else 20     # data parallel: decisions only one rank can make are agreed on every 20 steps
     device = session.engine.device
     while args.steps is None or session.global_step < args.steps:
+        multiscale.follow(session, schedule)         # (no schedule: nothing; otherwise the size of this step, logged when it changes)
         images, labels = data.next()
         session.step(images, labels)
         n_rate += 1

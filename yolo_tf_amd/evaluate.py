@@ -266,10 +266,15 @@ class EvalData(object):
     The resize is the device's TF-style bilinear one (yolo2_augment_images with the full-image crop and no flags), the one training
     sees.  It is NOT the PIL resize detect.py applies to a file, so scores can differ slightly from what detect.py prints."""
 
-    def __init__(self, images, objects, batch, width, height, cell_width, cell_height, difficult=None, crowd=None, area=None):
+    def __init__(self, images, objects, batch, width, height, cell_width, cell_height, difficult=None, crowd=None, area=None, input_sizes=None):
+        """``input_sizes``: optional list of (width, height) the data can be walked at (``set_size``; width x height comes first): the
+        decoded dataset is uploaded once, the batch buffer is allocated for the largest of them, the ground truth in cell units is
+        recomputed for the grid of each (the network's stride is what width / cell_width and height / cell_height say)."""
         # the training pipeline with every augmentation disabled: its draw() then yields the full-image crop and no flags
-        self.pipe = DeviceInputPipeline(images, objects, batch, width, height, None, cell_width, cell_height, config=AugmentConfig(None))
+        self.pipe = DeviceInputPipeline(images, objects, batch, width, height, None, cell_width, cell_height, config=AugmentConfig(None),
+                                        sizes=input_sizes)
         self.B, self.sizes = batch, self.pipe.sizes
+        self._objects, self._difficult = objects, difficult
         self.gt = gt_in_cells(objects, self.sizes, cell_width, cell_height, difficult)
         self.area, self.flags = [], []
         for i, (c, b) in enumerate(objects):
@@ -280,6 +285,14 @@ class EvalData(object):
             assert len(self.area[i]) == len(self.flags[i]) == len(b)
         self.scale = np.array([[w / cell_width, h / cell_height] for w, h in self.sizes], np.float32).reshape(-1, 2)
         self._keep = None
+
+    def set_size(self, width, height):
+        """The input size (one of ``input_sizes``) of the batches that follow: the images are resized to it, boxes and scales are restated
+        in its cells.  Areas and flags are in source pixels and do not change."""
+        pipe = self.pipe
+        pipe.set_size(int(width), int(height))
+        self.gt = gt_in_cells(self._objects, self.sizes, pipe.cell_width, pipe.cell_height, self._difficult)
+        self.scale = np.array([[w / pipe.cell_width, h / pipe.cell_height] for w, h in self.sizes], np.float32).reshape(-1, 2)
 
     def __len__(self):
         return (len(self.sizes) + self.B - 1) // self.B

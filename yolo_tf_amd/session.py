@@ -333,11 +333,27 @@ class TrainSession(object):
 class DetectSession(object):
     """Forward with moving-average BN + decode + batched on-GPU NMS (detect.py:69-80)."""
 
-    def __init__(self, builder, batch_size=1, dtype='bf16', seed=0, calibration=None):
+    def __init__(self, builder, batch_size=1, dtype='bf16', seed=0, calibration=None, sizes=None):
+        """``sizes``: optional list of (width, height) input sizes one set of weights is run at (YOLO9000, table 3); the network is traced at
+        each, the buffers are allocated once for the largest, ``set_size`` switches between them and the builder's configured size is
+        selected first.  Not with ``dtype='int8'``: a calibration's engine binds one size."""
         assert not builder.training
         self.builder = builder
-        self.model = m = builder.model
         self.v1 = getattr(builder, 'family', 'yolo2') == 'yolo'
+        own = (builder.width, builder.height)
+        traced = {own: (builder.graph, builder.model)}
+        if sizes:
+            if dtype == 'int8':
+                raise ValueError("dtype='int8' with sizes: quantised inference binds one input size (QuantEngine); run one session per size")
+            if self.v1:
+                raise ValueError('sizes: the fully connected YOLO (v1) head fixes the input size')
+            for wh in sizes:
+                wh = (int(wh[0]), int(wh[1]))
+                if wh not in traced:
+                    traced[wh] = builder.trace(wh[0], wh[1], training=False)
+        largest = max(traced, key=lambda wh: wh[0] * wh[1])
+        if not all(w <= largest[0] and h <= largest[1] for w, h in traced):
+            raise ValueError('sizes: one size must contain all the others')
         if dtype == 'int8':
             # post-training quantised inference (yolo_tf_amd/quant.py): int8 activations and filters, bf16 logits -- decode, NMS and the
             # evaluators below read those and do not change
@@ -350,21 +366,54 @@ class DetectSession(object):
                 calibration = Calibration.load(calibration)
             self.engine = QuantEngine(builder.graph, batch_size, calibration, seed=seed)
         else:
-            self.engine = Engine(builder.graph, batch_size, dtype, training=False, seed=seed)
-        dev = self.engine.device
+            self.engine = Engine(traced[largest][0], batch_size, dtype, training=False, seed=seed)
+        e = self.engine
+        dev = e.device
+        for wh, (g, _) in traced.items():
+            if wh != largest:
+                e.add_size(g)
+        if len(traced) > 1:
+            # the filters are folded with their BN statistics once, for the layers the binding current at that time does not fuse with a
+            # pool: every size must fuse the same layers (true of sizes that are multiples of the network's stride)
+            fused = set(tuple(sorted(t.name for t in bnd['fused_pool'])) for bnd in e._bindings.values())
+            if len(fused) != 1:
+                raise ValueError('sizes: the network fuses different layers with their pools at these sizes')
+        self.models = {wh: gm[1] for wh, gm in traced.items()}
+        m = traced[largest][1]
         self.B, self.A, self.C = batch_size, (m.boxes_per_cell if self.v1 else len(m.anchors)), m.classes
         n = m.cells * self.A
-        self.N = n
         self.anchors = None if self.v1 else torch.from_numpy(m.anchors.reshape(-1)).to(dev)
-        self.conf = torch.zeros(batch_size, n, self.C, dtype=torch.float32, device=dev)
-        self.xy_min = torch.zeros(batch_size, n, 2, dtype=torch.float32, device=dev)
-        self.xy_max = torch.zeros(batch_size, n, 2, dtype=torch.float32, device=dev)
-        self.order = torch.zeros(batch_size, n, dtype=torch.int32, device=dev)
+        # allocated once for the largest N; every size reads and writes contiguous views at the start
+        conf = torch.zeros(batch_size * n * self.C, dtype=torch.float32, device=dev)
+        xy_min = torch.zeros(batch_size * n * 2, dtype=torch.float32, device=dev)
+        xy_max = torch.zeros(batch_size * n * 2, dtype=torch.float32, device=dev)
+        order = torch.zeros(batch_size * n, dtype=torch.int32, device=dev)
+        self._outputs = {}
+        for wh, mdl in self.models.items():
+            k = mdl.cells * self.A
+            self._outputs[wh] = (k, conf[:batch_size * k * self.C].view(batch_size, k, self.C), xy_min[:batch_size * k * 2].view(batch_size, k, 2),
+                                 xy_max[:batch_size * k * 2].view(batch_size, k, 2), order[:batch_size * k].view(batch_size, k))
         self.nan_flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._attrs = None
-        m.bind(self)                 # Model.conf / xy_min / xy_max / iou / prob / xy / wh read this session's buffers
-        self.nms_ws = torch.zeros(ops.workspace_bytes('nms', batch_size, n, self.C) // 4, dtype=torch.int32, device=dev)
+        self._attrs_by_size = {}
+        self.nms_ws = torch.zeros(max(ops.workspace_bytes('nms', batch_size, o[0], self.C) for o in self._outputs.values()) // 4,
+                                  dtype=torch.int32, device=dev)
         self.async_errors = ops.AsyncErrorPoll()
+        self.size = None
+        self.set_size(*own)
+
+    def set_size(self, width, height):
+        """Input size of the following runs (one of the sizes the session was built with); the variables are shared."""
+        wh = (int(width), int(height))
+        if wh not in self.models:
+            raise KeyError('input size %dx%d is not one of the sizes the session was built with' % wh)
+        if len(self.models) > 1:
+            self.engine.set_size(wh[1], wh[0])
+        self.model = self.models[wh]
+        self.N, self.conf, self.xy_min, self.xy_max, self.order = self._outputs[wh]
+        self._attrs = self._attrs_by_size.get(wh)
+        self._attrs_valid = False
+        self.model.bind(self)        # Model.conf / xy_min / xy_max / iou / prob / xy / wh read this session's buffers
+        self.size = wh
 
     def run(self, images, preprocess_mode=0, check_numerics=True):
         """images: device f32 [B,H,W,3].  Returns device tensors conf [B,N,C], xy_min, xy_max [B,N,2]
@@ -399,6 +448,7 @@ class DetectSession(object):
                            'prob': torch.zeros(self.B, self.N, self.C, dtype=torch.float32, device=dev),
                            'xy': torch.zeros(self.B, self.N, 2, dtype=torch.float32, device=dev),
                            'wh': torch.zeros(self.B, self.N, 2, dtype=torch.float32, device=dev)}
+            self._attrs_by_size[self.size] = self._attrs
             self._attrs_valid = False
         if not getattr(self, '_attrs_valid', False):
             e, m, a = self.engine, self.model, self._attrs

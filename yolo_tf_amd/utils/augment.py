@@ -95,9 +95,16 @@ class DeviceInputPipeline(object):
 
     images: list of uint8 [h, w, 3] arrays (any sizes); objects: list of (classes int [K], coords float [K,4] pixels).
     ``next(session)`` fills the session's label buffers in place and returns the f32 [B,H,W,3] image batch (0..255) that
-    ``TrainSession.step`` standardises."""
+    ``TrainSession.step`` standardises.
 
-    def __init__(self, images, objects, batch, width, height, classes, cell_width, cell_height, config=None, seed=0, rank=0, world=1):
+    ``sizes``: optional list of (width, height) for multi-scale training; ``downsampling`` = (dw, dh) of the network (default: what width /
+    cell_width and height / cell_height say).  The output is then allocated once, for the largest size, and ``next(session)`` produces the
+    batch and the labels for ``session.size``: a contiguous [B,h,w,3] view at the start of that buffer, on a grid of w // dw x h // dh.  The
+    host draws do not depend on the output size, so a size change never shifts the random stream.  Without ``sizes`` there is one size and
+    one buffer of exactly its shape."""
+
+    def __init__(self, images, objects, batch, width, height, classes, cell_width, cell_height, config=None, seed=0, rank=0, world=1,
+                 sizes=None, downsampling=None):
         assert len(images) == len(objects) and len(images) > 0
         self.cfg = config if isinstance(config, AugmentConfig) else AugmentConfig(config)
         self.B, self.W, self.H, self.classes = batch, width, height, classes
@@ -111,7 +118,17 @@ class DeviceInputPipeline(object):
         self.src = torch.from_numpy(packed).cuda()
         self.objects = [(np.asarray(c, np.int32).reshape(-1), np.asarray(b, np.float32).reshape(-1, 4)) for c, b in objects]
         dev = self.src.device
-        self.out = torch.zeros(batch, height, width, 3, dtype=torch.float32, device=dev)
+        self._views = None
+        if sizes:
+            self.downsampling = tuple(int(d) for d in downsampling) if downsampling is not None else (width // cell_width, height // cell_height)
+            assert (cell_width * self.downsampling[0], cell_height * self.downsampling[1]) == (width, height)
+            every = sorted(set((int(w), int(h)) for w, h in sizes) | {(width, height)})
+            assert all(w % self.downsampling[0] == 0 and h % self.downsampling[1] == 0 for w, h in every), 'sizes must be multiples of the downsampling'
+            self.buffer = torch.zeros(batch * max(w * h for w, h in every) * 3, dtype=torch.float32, device=dev)
+            self._views = {(w, h): self.buffer[:batch * h * w * 3].view(batch, h, w, 3) for w, h in every}
+            self.out = self._views[(width, height)]
+        else:
+            self.out = self.buffer = torch.zeros(batch, height, width, 3, dtype=torch.float32, device=dev)
         self.ws = torch.zeros(3 * batch, dtype=torch.float64, device=dev)
         self.err = torch.zeros(1, dtype=torch.int32, device=dev)
 
@@ -151,7 +168,19 @@ class DeviceInputPipeline(object):
         self._keep = (params, cls_d, box_d, first_d)      # alive until the next launch (asynchronous kernels)
         return self.out
 
+    def set_size(self, width, height):
+        """Multi-scale: the size (one of ``sizes``) of the batches and label grids that follow."""
+        if (width, height) == (self.W, self.H):
+            return
+        if self._views is None or (width, height) not in self._views:
+            raise KeyError('input size %dx%d is not one of the sizes the pipeline was built with' % (width, height))
+        self.W, self.H = width, height
+        self.cell_width, self.cell_height = width // self.downsampling[0], height // self.downsampling[1]
+        self.out = self._views[(width, height)]
+
     def next(self, session):
+        if self._views is not None:
+            self.set_size(*session.size)
         arr, cls, box, first = self.assemble(self.sample())
         return self.launch(arr, cls, box, first, session.labels)
 
