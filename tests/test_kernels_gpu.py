@@ -3,7 +3,9 @@ Bit-exact for moves / integer decisions (reorg, pool routing, NMS keep-sets, fil
 1e-4 relative for fp32 arithmetic (BASELINE.json north_star); bf16 mode is compared with the
 oracle run on the bf16-rounded inputs at a bf16-sized tolerance (stated per test).  The batch-norm family is covered here at the
 network's own channel counts and well-conditioned inputs; its conditioning, the other channel counts, per-element bf16 bounds and the
-decision points (z == 0, pool ties) are tests/test_bn_gpu.py's, as the head kernels are tests/test_head_gpu.py's and NMS tests/test_nms_gpu.py's."""
+decision points (z == 0, pool ties) are tests/test_bn_gpu.py's, as the head kernels are tests/test_head_gpu.py's and NMS tests/test_nms_gpu.py's.
+The optimizers, the two clips, scale, zero_ranges and bn_fold are checked here on one size and one step; step by step, per element and at
+the sizes, alignments and edge cases where csrc/optim.hip takes another path: tests/test_optim_gpu.py."""
 import ctypes
 import os
 

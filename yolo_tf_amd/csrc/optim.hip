@@ -197,6 +197,9 @@ extern "C" int yolo2_adadelta(float *w, const float *g, float *acc, float *acc_u
 }
 
 // per-tensor clip_by_norm: one block row per segment (grid.y = segment), two passes
+// [TF-sem] tf.clip_by_norm: g * clip / max(norm, clip).  fmaxf returns clip for a NaN norm, which would leave a tensor that holds a NaN unscaled;
+// TF's maximum (and the oracle's) keeps the NaN and the whole tensor becomes NaN.  One select per workgroup, nothing per element.
+__device__ __forceinline__ float clip_scale(float norm, float clip) { return norm == norm ? clip / fmaxf(norm, clip) : norm; }
 __global__ void seg_sumsq_kernel(const float *__restrict__ g, const long *__restrict__ seg_off, double *__restrict__ ws) {
     const int s = blockIdx.y;
     const long beg = seg_off[s], end = seg_off[s + 1];
@@ -232,7 +235,7 @@ __global__ void seg_scale_fixed_kernel(float *__restrict__ g, const long *__rest
     double t = 0.0;
     for (int b = 0; b < Y2_CLIP_PARTS; ++b) t += part[(long)s * Y2_CLIP_PARTS + b];
     const float norm = (float)sqrt(t);
-    const float scale = clip / fmaxf(norm, clip);
+    const float scale = clip_scale(norm, clip);
     if (scale == 1.0f) return;
     for (long i = beg + blockIdx.x * (long)blockDim.x + threadIdx.x; i < end; i += (long)gridDim.x * blockDim.x) g[i] = g[i] * scale;
 }
@@ -240,7 +243,7 @@ __global__ void seg_scale_kernel(float *__restrict__ g, const long *__restrict__
     const int s = blockIdx.y;
     const long beg = seg_off[s], end = seg_off[s + 1];
     const float norm = (float)sqrt(ws[s]);
-    const float scale = clip / fmaxf(norm, clip);
+    const float scale = clip_scale(norm, clip);
     if (scale == 1.0f) return;
     for (long i = beg + blockIdx.x * (long)blockDim.x + threadIdx.x; i < end; i += (long)gridDim.x * blockDim.x) g[i] = g[i] * scale;
 }
