@@ -44,11 +44,11 @@ def detect(sess, names, path, args):
     image_width, image_height = _image.size
     resized = np.asarray(_image.resize((width, height)), np.uint8).astype(np.float32)
     conf, xy_min, xy_max = sess.run(torch.from_numpy(resized[None]).cuda(), PREPROCESS[args.preprocess])   # raises on NaN/Inf
-    order = sess.nms(args.threshold, args.threshold_iou)[0].cpu().numpy()
+    order = sess.nms(args.threshold, args.threshold_iou, args.nms, args.sigma)[0].cpu().numpy()
     conf, xy_min, xy_max = conf[0].cpu().numpy(), xy_min[0].cpu().numpy(), xy_max[0].cpu().numpy()
     scale = np.array([image_width / model.cell_width, image_height / model.cell_height], np.float32)
     results = []
-    for i in order:                                   # same traversal order as the reference's box list
+    for i in order:                                   # the reference's box list order (--nms hard) or best final score first (Soft-NMS)
         index = int(np.argmax(conf[i]))
         if conf[i, index] > args.threshold:
             (x0, y0), (x1, y1) = xy_min[i] * scale, xy_max[i] * scale
@@ -84,6 +84,7 @@ def main():
     builder = yolo.Builder(args, config)
     builder(None)
     dtype = args.dtype or (config.get('mi355x', 'dtype') if config.has_option('mi355x', 'dtype') else 'bf16')
+    args.nms, args.sigma = utils.nms_options(args, config)      # --nms / --sigma, else [mi355x] nms / nms_sigma, else hard
     from yolo_tf_amd import tf_checkpoint
     logdir = utils.get_logdir(config)
     calibration = None
@@ -111,7 +112,7 @@ def main():
             draw(_path, results, os.path.join(args.output, os.path.basename(_path) + '.png'))
 
 
-def make_args():
+def make_args(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument('path', help='input image path')
     parser.add_argument('-c', '--config', nargs='+', default=['config.ini'], help='config file')
@@ -124,7 +125,10 @@ def make_args():
     parser.add_argument('--dtype', default=None, choices=['bf16', 'f32', 'int8'], help="'int8': post-training quantised inference (needs a calibration)")
     parser.add_argument('--calibration', default=None, help='--dtype int8: the file quantize.py wrote (default: calibration.npz in the logdir)')
     parser.add_argument('--ema', action='store_true', help='use the moving averages of the weights a run with [mi355x] ema_decay keeps in its checkpoints')
-    return parser.parse_args()
+    parser.add_argument('--nms', default=None, choices=list(utils.NMS_METHODS),
+                        help="suppression: 'hard' (the reference's NMS; the default) or Soft-NMS with 'linear' or 'gaussian' decay; default [mi355x] nms")
+    parser.add_argument('--sigma', type=float, default=None, help='--nms gaussian: the decay is exp(-IoU^2 / sigma), at least 1/64 (default [mi355x] nms_sigma, else 0.5)')
+    return parser.parse_args(argv)
 
 
 if __name__ == '__main__':

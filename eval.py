@@ -53,6 +53,7 @@ def main():
     builder = yolo.Builder(args, config)
     builder(None)
     dtype = args.dtype or (config.get('mi355x', 'dtype') if config.has_option('mi355x', 'dtype') else 'bf16')
+    args.nms, args.sigma = utils.nms_options(args, config)      # --nms / --sigma, else [mi355x] nms / nms_sigma, else hard
     logdir = utils.get_logdir(config)
     calibration = None
     if dtype == 'int8':       # post-training quantised inference: the scales quantize.py measured for this checkpoint
@@ -87,11 +88,12 @@ def main():
                              crowd=crowd, area=area, input_sizes=sizes)
     extra = dict(names=list(builder.names), images=len(images), checkpoint=model_path or tf_path, global_step=int(step), calibration=calibration, ema=bool(args.ema),
                  config={k: getattr(args, k) for k in ('config', 'profile', 'data', 'batch_size', 'threshold', 'threshold_iou', 'iou', 'mode', 'protocol',
-                                                       'preprocess', 'dtype', 'limit', 'images', 'seed')})
+                                                       'preprocess', 'dtype', 'limit', 'images', 'seed', 'nms', 'sigma')})
 
     def run(on_batch=None):
         return evaluate.evaluate(builder, sess, data, mode=args.mode, threshold=args.threshold, threshold_iou=args.threshold_iou, iou=args.iou,
-                                 preprocess_mode=PREPROCESS[args.preprocess], max_records=args.max_records, protocol=args.protocol, on_batch=on_batch)
+                                 preprocess_mode=PREPROCESS[args.preprocess], max_records=args.max_records, protocol=args.protocol, on_batch=on_batch,
+                                 nms=args.nms, sigma=args.sigma)
     if sizes is None:
         result = run()
         out = report(args, builder, result)
@@ -171,6 +173,9 @@ def make_args(argv=None):
     parser.add_argument('--sizes', default=None, help="evaluate the one checkpoint at several input sizes: entries S, WxH or LO-HI (squares in steps of the "
                         "network's stride) separated by spaces or commas, e.g. '320-608'; prints one table per size and a closing one, --json gets by_size")
     parser.add_argument('--ema', action='store_true', help='use the moving averages of the weights a run with [mi355x] ema_decay keeps in its checkpoints')
+    parser.add_argument('--nms', default=None, choices=list(utils.NMS_METHODS),
+                        help="suppression: 'hard' (the reference's NMS; the default) or Soft-NMS with 'linear' or 'gaussian' decay; default [mi355x] nms")
+    parser.add_argument('--sigma', type=float, default=None, help='--nms gaussian: the decay is exp(-IoU^2 / sigma), at least 1/64 (default [mi355x] nms_sigma, else 0.5)')
     parser.add_argument('--level', default='info', help='logging level')
     return parser.parse_args(argv)
 

@@ -422,6 +422,24 @@ int yolo2_l2_regularizer(const float *w, float *g, long n, float scale, double *
 int yolo2_nms(float *conf, const float *xy_min, const float *xy_max, int *order_out, int *ws,
               int B, int N, int C, float threshold, float threshold_iou, void *stream);
 
+/* ---- Soft-NMS (Bodla et al., ICCV 2017; new work, the reference has none), batched over images and classes ---------------
+ * Per (image, class): the candidates are the boxes with conf > threshold (NaN is none).  The best remaining candidate by (score
+ * descending, box index ascending) is picked -- its score is final -- and every other remaining candidate's score is multiplied by
+ *   YOLO2_NMS_HARD      IoU >= threshold_iou ? 0 : 1
+ *   YOLO2_NMS_LINEAR    IoU >= threshold_iou ? 1 - IoU : 1
+ *   YOLO2_NMS_GAUSSIAN  soft_exp(-(IoU * IoU) / sigma)      (csrc/soft_exp.h; threshold_iou is unused)
+ * then the best is selected again, until none is left above `threshold`.  Picked boxes keep their final score, every other candidate is
+ * written as +0.0f, non-candidates are not touched.  IoU as in yolo2_nms (`>=`, not the paper's `>`); f32, bit for bit reproducible.
+ * conf [B,N,C] is updated in place; xy_min / xy_max [B,N,2] finite with xy_min <= xy_max.  order_out [B,N] (int, may be NULL) receives per
+ * image the box indices by (max over classes of the FINAL scores descending, box index ascending), written by a second launch.
+ * 1 <= N <= 4096, threshold >= 0, threshold_iou finite, sigma finite and >= 1/64 (Gaussian only); anything else is YOLO2_E_ARG before any
+ * HIP call.  No workspace.  Per class only: there is no class-agnostic mode and no limit on the number of detections. */
+#define YOLO2_NMS_HARD 0
+#define YOLO2_NMS_LINEAR 1
+#define YOLO2_NMS_GAUSSIAN 2
+int yolo2_soft_nms(float *conf, const float *xy_min, const float *xy_max, int *order_out, int B, int N, int C, int method,
+                   float threshold, float threshold_iou, float sigma, void *stream);
+
 /* ---- optimizers: train.py:70-80 (TF-1.0 Apply* kernels), flat f32 buffers of n elements ------ */
 int yolo2_adam(float *w, const float *g, float *m, float *v, long n, float alpha, float beta1,
                float beta2, float eps, float gscale, void *stream);   /* alpha = lr*sqrt(1-b2^t)/(1-b1^t) */

@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get('YOLO2_LIB_PATH') or os.path.join(_HERE, 'csrc', 'liby
 
 F32, BF16 = 0, 1
 I8_OUT_I8, I8_OUT_BF16, I8_OUT_F32, I8_OUT_ACC = 0, 1, 2, 3      # out_kind of yolo2_conv2d_i8
+NMS_METHODS = {'hard': 0, 'linear': 1, 'gaussian': 2}               # YOLO2_NMS_*: method of yolo2_soft_nms
 
 
 class HipKernelError(RuntimeError):
@@ -83,6 +84,7 @@ SIGNATURES = {
     'yolo2_dropout_bwd': [_p, _p, _p, _l, _f, _i, _p],
     'yolo2_l2_regularizer': [_p, _p, _l, _f, _p, _p],
     'yolo2_nms': [_p, _p, _p, _p, _p, _i, _i, _i, _f, _f, _p],
+    'yolo2_soft_nms': [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _p],
     'yolo2_adam': [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _p],
     'yolo2_momentum': [_p, _p, _p, _l, _f, _f, _f, _p],
     'yolo2_sgd': [_p, _p, _l, _f, _f, _p],

@@ -28,6 +28,7 @@ SOURCES = {
     'head.hip': ['-ffp-contract=off'],
     'yolo1.hip': ['-ffp-contract=off'],
     'nms.hip': ['-ffp-contract=off'],
+    'soft_nms.hip': ['-ffp-contract=off'],
     'augment.hip': ['-ffp-contract=off'],
     'eval.hip': ['-ffp-contract=off'],
     'eval_coco.hip': ['-ffp-contract=off'],

@@ -369,11 +369,12 @@ def device_gt_coco(cls, box, area, flags, first, scale, device='cuda'):
 
 
 def evaluate(builder, session, data, mode='detect', threshold=0.005, threshold_iou=0.45, iou=0.5, preprocess_mode=0, max_records=None,
-             evaluator=None, on_batch=None, protocol='voc'):
+             evaluator=None, on_batch=None, protocol='voc', nms='hard', sigma=0.5):
     """Runs ``session`` (a DetectSession whose batch equals data.B) over ``data`` (an EvalData) and returns Evaluator.result().
     threshold / threshold_iou go to detect() (score threshold and the NMS overlap), iou is the matching threshold.  on_batch(session, gt,
     image_base, n_valid), if given, is called after every detect (tests download the batch there).  protocol 'coco' scores with a
-    CocoEvaluator instead (``iou`` is unused: its thresholds are the evaluator's table) and returns CocoEvaluator.result()."""
+    CocoEvaluator instead (``iou`` is unused: its thresholds are the evaluator's table) and returns CocoEvaluator.result().  nms / sigma
+    choose the suppression of detect(): 'hard' (the reference's), or Soft-NMS 'linear' / 'gaussian'."""
     assert session.B == data.B, 'the session runs batches of %d, the data yields %d' % (session.B, data.B)
     if protocol not in ('voc', 'coco'):
         raise ValueError("protocol must be 'voc' or 'coco', not %r" % (protocol,))
@@ -385,7 +386,7 @@ def evaluate(builder, session, data, mode='detect', threshold=0.005, threshold_i
         per_image = session.N * (session.C if mode == 'all' else 1)
         evaluator = Evaluator(session.C, max_records or n * per_image, mode=mode, threshold=threshold, iou_threshold=iou)
     for images, gt, base, n_valid in data.batches(protocol):
-        conf, xy_min, xy_max, _ = session.detect(images, threshold, threshold_iou, preprocess_mode)
+        conf, xy_min, xy_max, _ = session.detect(images, threshold, threshold_iou, preprocess_mode, nms=nms, sigma=sigma)
         evaluator.add(conf, xy_min, xy_max, *gt, image_base=base, n_valid=n_valid)
         if on_batch is not None:
             on_batch(session, gt, base, n_valid)

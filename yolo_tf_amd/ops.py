@@ -334,6 +334,15 @@ def nms(conf, xy_min, xy_max, order, ws, B, N, C, thr, thr_iou):
     call('yolo2_nms', ptr(conf), ptr(xy_min), ptr(xy_max), ptr(order), ptr(ws), B, N, C, thr, thr_iou, _stream())
 
 
+def soft_nms(conf, xy_min, xy_max, order, B, N, C, method, thr, thr_iou, sigma=0.5):
+    """yolo2_soft_nms: method 'hard', 'linear' or 'gaussian' (or its YOLO2_NMS_* code); order may be None."""
+    if isinstance(method, str):
+        if method not in _lib.NMS_METHODS:
+            raise ValueError('nms method must be one of %s, not %r' % (', '.join(_lib.NMS_METHODS), method))
+        method = _lib.NMS_METHODS[method]
+    call('yolo2_soft_nms', ptr(conf), ptr(xy_min), ptr(xy_max), ptr(order), B, N, C, int(method), thr, thr_iou, sigma, _stream())
+
+
 def adam(w, g, m, v, n, alpha, b1, b2, eps, gscale=1.0):
     call('yolo2_adam', ptr(w), ptr(g), ptr(m), ptr(v), n, alpha, b1, b2, eps, gscale, _stream())
 

@@ -457,12 +457,18 @@ class DetectSession(object):
             self._attrs_valid = True
         return self._attrs
 
-    def nms(self, threshold=0.3, threshold_iou=0.4):
-        """In-place batched NMS on the decoded boxes; returns order [B,N] (reference list order)."""
-        ops.nms(self.conf, self.xy_min, self.xy_max, self.order, self.nms_ws, self.B, self.N, self.C, float(threshold), float(threshold_iou))
+    def nms(self, threshold=0.3, threshold_iou=0.4, method='hard', sigma=0.5):
+        """In-place batched NMS on the decoded boxes; returns order [B,N].  method 'hard' is the reference's NMS (csrc/nms.hip; the order is
+        the reference's list order); 'linear' and 'gaussian' are Soft-NMS (csrc/soft_nms.hip; the order is by final score, best first)."""
+        if method == 'hard':
+            ops.nms(self.conf, self.xy_min, self.xy_max, self.order, self.nms_ws, self.B, self.N, self.C, float(threshold), float(threshold_iou))
+        elif method in ('linear', 'gaussian'):
+            ops.soft_nms(self.conf, self.xy_min, self.xy_max, self.order, self.B, self.N, self.C, method, float(threshold), float(threshold_iou), float(sigma))
+        else:
+            raise ValueError("nms method must be 'hard', 'linear' or 'gaussian', not %r" % (method,))
         return self.order
 
-    def detect(self, images, threshold=0.3, threshold_iou=0.4, preprocess_mode=0):
+    def detect(self, images, threshold=0.3, threshold_iou=0.4, preprocess_mode=0, nms='hard', sigma=0.5):
         self.run(images, preprocess_mode, check_numerics=False)
-        self.nms(threshold, threshold_iou)
+        self.nms(threshold, threshold_iou, nms, sigma)
         return self.conf, self.xy_min, self.xy_max, self.order

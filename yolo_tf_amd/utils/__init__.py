@@ -66,6 +66,20 @@ def ensure_names(config):
     return dst
 
 
+NMS_METHODS = ('hard', 'linear', 'gaussian')
+
+
+def nms_options(args, config):
+    """(method, sigma) of detect.py / eval.py: --nms / --sigma, else [mi355x] nms / nms_sigma, else ('hard', 0.5)."""
+    method = getattr(args, 'nms', None) or (config.get('mi355x', 'nms') if config.has_option('mi355x', 'nms') else 'hard')
+    sigma = getattr(args, 'sigma', None)
+    if sigma is None:
+        sigma = config.getfloat('mi355x', 'nms_sigma') if config.has_option('mi355x', 'nms_sigma') else 0.5
+    if method not in NMS_METHODS:
+        raise ValueError('[mi355x] nms must be one of %s, not %r' % (', '.join(NMS_METHODS), method))
+    return method, float(sigma)
+
+
 def make_config(paths, basedir=None):
     """ConfigParser from overlay files (+ optional basedir override) -- convenience for scripts/tests."""
     import configparser
