@@ -727,6 +727,10 @@ def detect(spec, params, x, classes, anchors, threshold=0.3, threshold_iou=0.4):
 # here: PARITY UNPINNED for these functions -- they restate the published TF-1.0 kernels ([TF-sem]:
 # ResizeBilinear align_corners=False, RGBToHSV / HSVToRGB, AdjustContrastv2, rgb_to_grayscale weights) in float32
 # in the kernels' operation order.  The box arithmetic (random_crop, flip, resize factor) is the reference's own.
+# One point departs from a literal reading of HSVToRGB's switch: rgb_to_hsv wraps a negative hue with h + 1, which for
+# |h| < 2^-25 rounds to exactly 1.0 in f32; dh is then 6, which a literal switch sends to its default branch, (m, m, m):
+# the dominant channel is lost.  Hue is periodic, so hsv_to_rgb treats dh == 6 as sector 5 (fmodu is 0 there, the result
+# is (c + m, m, m), the value at hue 0); csrc/augment.hip does the same.
 # ---------------------------------------------------------------------------------------------------------
 def random_crop_box(objects_coord, width_height, u4, scale):
     """utils/preprocess.py:28-42 given the four uniforms u4 ~ U(0, scale) it draws.  objects_coord [K,4] pixels.
@@ -810,7 +814,7 @@ def hsv_to_rgb(hsv):
     fmodu = np.where(fmodu <= 0, fmodu + f(2) * np.ceil((-fmodu) / f(2) + (fmodu == np.floor(fmodu / 2) * 2)), fmodu)   # while (<= 0) += 2
     fmodu = (fmodu - f(2) * np.floor(fmodu / f(2))).astype(f)            # while (>= 2) -= 2
     x = c * (f(1) - np.abs(fmodu - f(1)))
-    cat = dh.astype(np.int32)
+    cat = np.where(dh == f(6), 5, dh.astype(np.int32))                   # hue exactly 1.0 is hue 0: sector 5 with x = 0
     z = np.zeros_like(c)
     rr = np.select([cat == 0, cat == 1, cat == 4, cat == 5], [c, x, x, c], z)
     gg = np.select([cat == 0, cat == 1, cat == 2, cat == 3], [x, c, c, x], z)

@@ -54,6 +54,10 @@ def test_colour_ops_known_answers():
     np.testing.assert_allclose(R.adjust_hue(img, 0.0), img, atol=3e-4)
     third = R.adjust_hue(np.array([[[200, 10, 10]]], np.float32), 1.0 / 3.0)          # red -> green
     np.testing.assert_allclose(third, [[[10, 200, 10]]], atol=1e-3)
+    # a tiny negative hue wraps to exactly 1.0f: hue is periodic, the dominant channel stays (a literal HSVToRGB switch gives (81, 81, 81))
+    edge = R.adjust_saturation(np.array([[[201, np.nextafter(np.float32(101), np.float32(0)), 101]]], np.float32), 1.2)
+    assert R.rgb_to_hsv(np.array([[[201, np.nextafter(np.float32(101), np.float32(0)), 101]]], np.float32))[0, 0, 0] == np.float32(1)
+    np.testing.assert_allclose(edge, [[[201, 81, 81]]], atol=1e-3)
 
 
 def test_box_transforms_follow_the_reference_arithmetic():

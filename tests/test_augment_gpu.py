@@ -23,15 +23,18 @@ def ops():
     return o
 
 
-def run_augment(ops, images, params, W, H):
+def run_augment(ops, images, params, W, H, offsets=None, src=None):
+    """One launch.  By default the images are packed back to back; `offsets` (bytes, one per image) and `src` (a device uint8 buffer that
+    already holds them there) place them elsewhere, e.g. several entries on one source."""
     from yolo_tf_amd._lib import AugmentParams
     from yolo_tf_amd.utils import augment as A
     B = len(images)
     arr = (AugmentParams * B)()
-    off = 0
-    for d, im, p in zip(arr, images, params):
-        d.src_offset, d.src_w, d.src_h = off, im.shape[1], im.shape[0]
-        off += im.size
+    if offsets is None:
+        offsets = np.cumsum([0] + [im.size for im in images])[:-1]
+        src = torch.from_numpy(np.concatenate([im.reshape(-1) for im in images])).cuda()
+    for d, im, p, off in zip(arr, images, params, offsets):
+        d.src_offset, d.src_w, d.src_h = int(off), im.shape[1], im.shape[0]
         d.crop_x, d.crop_y, d.crop_w, d.crop_h = p.get('crop') or (0, 0, im.shape[1], im.shape[0])
         fl = 0
         for key, bit in (('flip', A.FLIP), ('gray', A.GRAY)):
@@ -45,7 +48,6 @@ def run_augment(ops, images, params, W, H):
             fl |= A.NOISE
             d.noise_scale, d.noise_seed = p['noise_scale'], p.get('noise_seed', 7)
         d.flags = fl
-    src = torch.from_numpy(np.concatenate([im.reshape(-1) for im in images])).cuda()
     pd = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).cuda()
     ws = torch.full((3 * B,), 9.0, dtype=torch.float64, device='cuda')          # dirty on purpose
     out = torch.zeros(B, H, W, 3, dtype=torch.float32, device='cuda')

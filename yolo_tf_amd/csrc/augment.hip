@@ -9,7 +9,11 @@
 // Box-Muller, resampled to |z| <= 2 like tf.truncated_normal).  The image arithmetic restates the TF-1.0 kernels in
 // f32 in their operation order (ResizeBilinear align_corners=False, RGBToHSV / HSVToRGB, AdjustContrastv2,
 // rgb_to_grayscale weights); oracle/yolo2_ref.py holds the same restatement (parity unpinned by the reference: the
-// arithmetic lives in TensorFlow).  HBM-bound: one uint8 source read (4 taps, L2-resident) + one f32 write per pixel;
+// arithmetic lives in TensorFlow).  One point departs from a literal reading of HSVToRGB's switch: rgb_to_hsv wraps a
+// negative hue with h + 1, which for |h| < 2^-25 rounds to exactly 1.0f; dh is then 6 and a literal switch falls to its
+// default and returns (m, m, m), losing the dominant channel.  Hue is periodic, so dh == 6 is treated as sector 5 here
+// and in the oracle (fmodu is 0 there: (c + m, m, m), the value at hue 0).
+// HBM-bound: one uint8 source read (4 taps, L2-resident) + one f32 write per pixel;
 // contrast needs the per-channel image mean of the value BEFORE contrast, so images that take that branch are
 // evaluated twice (pass A: sums, pass B: output) rather than staged.
 #include "common.h"
@@ -39,7 +43,7 @@ __device__ __forceinline__ Px hsv_to_rgb_tf(Px q) {
     while (fmodu <= 0.f) fmodu += 2.0f;
     while (fmodu >= 2.0f) fmodu -= 2.0f;
     const float x = c * (1.0f - fabsf(fmodu - 1.0f));
-    const int cat = (int)dh;
+    const int cat = dh == 6.0f ? 5 : (int)dh;       // hue exactly 1.0 (h + 1 rounded up) is hue 0: sector 5 with x = 0
     float rr = 0.f, gg = 0.f, bb = 0.f;
     switch (cat) {
         case 0: rr = c; gg = x; break;
