@@ -56,6 +56,37 @@ def detect(sess, names, path, args):
     return results
 
 
+def detect_tta(sess, names, path, args):
+    """detect() with test-time augmentation (--tta): the image is resized with PIL to every view's size as above, mirrored on the host for the
+    flipped views, and the views' boxes are fused on the device (Weighted Boxes Fusion).  Best fused score first."""
+    import torch
+    _image = read_image(path)
+    image_width, image_height = _image.size
+    sess.tta_begin()
+    for w, h, flip in sess.tta:
+        resized = np.asarray(_image.resize((w, h)), np.uint8).astype(np.float32)
+        if flip:
+            resized = np.ascontiguousarray(resized[:, ::-1])
+        sess.tta_add(torch.from_numpy(resized[None]).cuda(), (w, h, flip), args.threshold, args.threshold_iou, PREPROCESS[args.preprocess], args.nms, args.sigma)
+        if int(sess.nan_flag.item()) != 0:            # (tta_add does not synchronise; here every view is checked as sess.run checks one)
+            raise FloatingPointError('conf/xy_min/xy_max : Tensor had NaN or Inf values')
+    conf, xy_min, xy_max, rows = sess.tta_fuse(args.threshold, args.tta_iou)
+    sess.tta_check()                                   # per image: a cap that overflowed raises here
+    from yolo_tf_amd import ops
+    ops.check_async_errors()                           # a device-detected failure of any view raises as it does behind sess.run
+    n = int(rows[0].item())
+    conf, xy_min, xy_max = conf[0, :n].cpu().numpy(), xy_min[0, :n].cpu().numpy(), xy_max[0, :n].cpu().numpy()
+    model = sess.model                                 # the base view's: the fused boxes are in its cells
+    scale = np.array([image_width / model.cell_width, image_height / model.cell_height], np.float32)
+    index = conf.argmax(1) if n else np.zeros(0, np.int64)
+    score = conf[np.arange(n), index]
+    results = []
+    for i in np.argsort(-score, kind='stable'):
+        (x0, y0), (x1, y1) = xy_min[i] * scale, xy_max[i] * scale
+        results.append((names[index[i]], float(score[i]), float(x0), float(y0), float(x1), float(y1)))
+    return results
+
+
 def draw(path, results, out):
     import matplotlib
     matplotlib.use('Agg')
@@ -91,7 +122,16 @@ def main():
     if dtype == 'int8':       # post-training quantised inference: the scales quantize.py measured for this checkpoint
         from yolo_tf_amd import quant
         calibration = quant.calibration_path(logdir, args.calibration)
-    sess = DetectSession(builder, 1, dtype=dtype, calibration=calibration)
+    # test-time augmentation: --tta / --tta_iou, else [mi355x] tta / tta_iou
+    from yolo_tf_amd import tta
+    spec, args.tta_iou = tta.options(config, args.tta, args.tta_iou)
+    views = tta.parse_views(spec, (builder.width, builder.height), *(utils.get_downsampling(config) if model != 'yolo' else (1, 1)))
+    if views:
+        logging.info('test-time augmentation: views %s, fused at IoU %g' % (tta.describe(views), args.tta_iou))
+        if not tta.flip_only(views):
+            from yolo_tf_amd import multiscale
+            multiscale.check_nested(tta.view_sizes(views), '--tta %r' % spec)
+    sess = DetectSession(builder, 1, dtype=dtype, calibration=calibration, tta=views or None, tta_rows='evaluation' if views else None)
     model_path = checkpoint.latest_checkpoint(logdir)
     tf_path = None if model_path else tf_checkpoint.latest_checkpoint(logdir)      # a logdir the reference trained (tf.train.latest_checkpoint, detect.py:104)
     if model_path is None and tf_path is None:
@@ -103,7 +143,7 @@ def main():
     paths = [path] if os.path.isfile(path) else [os.path.join(d, f) for d, _, fs in os.walk(path) for f in fs
                                                  if os.path.splitext(f)[-1].lower() in args.exts]
     for _path in paths:
-        results = detect(sess, builder.names, _path, args)
+        results = (detect_tta if views else detect)(sess, builder.names, _path, args)
         print('%s: %d objects detected' % (_path, len(results)))
         for r in results:
             print('  %s %.1f%% (%.1f, %.1f)-(%.1f, %.1f)' % r)
@@ -128,6 +168,10 @@ def make_args(argv=None):
     parser.add_argument('--nms', default=None, choices=list(utils.NMS_METHODS),
                         help="suppression: 'hard' (the reference's NMS; the default) or Soft-NMS with 'linear' or 'gaussian' decay; default [mi355x] nms")
     parser.add_argument('--sigma', type=float, default=None, help='--nms gaussian: the decay is exp(-IoU^2 / sigma), at least 1/64 (default [mi355x] nms_sigma, else 0.5)')
+    parser.add_argument('--tta', default=None, help="test-time augmentation: 'flip' and / or sizes (S, WxH, LO-HI) separated by spaces or commas, e.g. "
+                        "'flip 320 608'; the image runs at each view and the boxes are fused on the device (Weighted Boxes Fusion); default [mi355x] tta")
+    parser.add_argument('--tta_iou', type=float, default=None, help='--tta: a box joins a fused box at this IoU or above (default [mi355x] tta_iou, else 0.55, '
+                        "the paper's default; not tuned here)")
     return parser.parse_args(argv)
 
 

@@ -74,7 +74,20 @@ def main():
         multiscale.check_nested(sorted(set(sizes) | {(builder.width, builder.height)}), '--sizes %r' % args.sizes)
         if dtype == 'int8':
             raise ValueError('--sizes with --dtype int8: quantised inference binds one input size; run eval.py once per size')
-    sess = DetectSession(builder, args.batch_size, dtype=dtype, calibration=calibration, sizes=sizes)
+    # test-time augmentation: --tta / --tta_iou, else [mi355x] tta / tta_iou; views fused on the device into ONE result
+    from yolo_tf_amd import tta
+    spec, args.tta_iou = tta.options(config, args.tta, args.tta_iou)
+    views = tta.parse_views(spec, (builder.width, builder.height), *(utils.get_downsampling(config) if model != 'yolo' else (1, 1)))
+    if views and sizes is not None:
+        raise ValueError('--tta %r with --sizes %r: --sizes makes one table per input size, --tta fuses its views into one result; give one of them'
+                         % (spec, args.sizes))
+    args.tta = tta.describe(views) if views else None
+    if views:
+        logging.info('test-time augmentation: views %s, fused at IoU %g' % (args.tta, args.tta_iou))
+        if not tta.flip_only(views):
+            from yolo_tf_amd import multiscale
+            multiscale.check_nested(tta.view_sizes(views), '--tta %r' % spec)
+    sess = DetectSession(builder, args.batch_size, dtype=dtype, calibration=calibration, sizes=sizes, tta=views or None, tta_rows='evaluation' if views else None)
     model_path = checkpoint.latest_checkpoint(logdir)
     tf_path = None if model_path else tf_checkpoint.latest_checkpoint(logdir)
     if model_path is None and tf_path is None:
@@ -85,15 +98,15 @@ def main():
     images, objects, difficult, crowd, area = load_data(args, config, len(builder.names))
     m = sess.model
     data = evaluate.EvalData(images, objects, args.batch_size, builder.width, builder.height, m.cell_width, m.cell_height, difficult=difficult,
-                             crowd=crowd, area=area, input_sizes=sizes)
+                             crowd=crowd, area=area, input_sizes=sizes if not views or tta.flip_only(views) else tta.view_sizes(views))
     extra = dict(names=list(builder.names), images=len(images), checkpoint=model_path or tf_path, global_step=int(step), calibration=calibration, ema=bool(args.ema),
                  config={k: getattr(args, k) for k in ('config', 'profile', 'data', 'batch_size', 'threshold', 'threshold_iou', 'iou', 'mode', 'protocol',
-                                                       'preprocess', 'dtype', 'limit', 'images', 'seed', 'nms', 'sigma')})
+                                                       'preprocess', 'dtype', 'limit', 'images', 'seed', 'nms', 'sigma', 'tta', 'tta_iou')})
 
     def run(on_batch=None):
         return evaluate.evaluate(builder, sess, data, mode=args.mode, threshold=args.threshold, threshold_iou=args.threshold_iou, iou=args.iou,
                                  preprocess_mode=PREPROCESS[args.preprocess], max_records=args.max_records, protocol=args.protocol, on_batch=on_batch,
-                                 nms=args.nms, sigma=args.sigma)
+                                 nms=args.nms, sigma=args.sigma, tta=views or None, fuse_iou=args.tta_iou)
     if sizes is None:
         result = run()
         out = report(args, builder, result)
@@ -176,6 +189,11 @@ def make_args(argv=None):
     parser.add_argument('--nms', default=None, choices=list(utils.NMS_METHODS),
                         help="suppression: 'hard' (the reference's NMS; the default) or Soft-NMS with 'linear' or 'gaussian' decay; default [mi355x] nms")
     parser.add_argument('--sigma', type=float, default=None, help='--nms gaussian: the decay is exp(-IoU^2 / sigma), at least 1/64 (default [mi355x] nms_sigma, else 0.5)')
+    parser.add_argument('--tta', default=None, help="test-time augmentation: 'flip' and / or sizes (S, WxH, LO-HI) separated by spaces or commas, e.g. "
+                        "'flip 320 608'; every batch runs at each view and the boxes are fused on the device (Weighted Boxes Fusion) into one result; "
+                        "default [mi355x] tta; not with --sizes")
+    parser.add_argument('--tta_iou', type=float, default=None, help='--tta: a box joins a fused box at this IoU or above (default [mi355x] tta_iou, else 0.55, '
+                        "the paper's default; not tuned here)")
     parser.add_argument('--level', default='info', help='logging level')
     return parser.parse_args(argv)
 

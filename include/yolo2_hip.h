@@ -440,6 +440,40 @@ int yolo2_nms(float *conf, const float *xy_min, const float *xy_max, int *order_
 int yolo2_soft_nms(float *conf, const float *xy_min, const float *xy_max, int *order_out, int B, int N, int C, int method,
                    float threshold, float threshold_iou, float sigma, void *stream);
 
+/* ---- test-time augmentation (new work, the reference has none): views of one image -> one frame -> Weighted Boxes Fusion ---------------
+ * A view is (width, height, flip); the base view is the first and its grid (cell_w0, cell_h0) is the frame of the result.
+ *
+ * yolo2_tta_gather: one view's conf [B,N,C], xy_min / xy_max [B,N,2] (cells of the view's grid (cw, ch)) -> rows offset .. offset+N-1 of
+ * the pooled out_conf [B,M,C], out_xy_min / out_xy_max [B,M,2]; no other row is touched.  sx = f32(cell_w0) / f32(cw) and sy =
+ * f32(cell_h0) / f32(ch) are the caller's (computed once, in f32).  x' = x * sx, or with flip xmin' = cell_w0 - xmax * sx and xmax' =
+ * cell_w0 - xmin * sx; y' = y * sy; conf is copied.  One elementwise launch.  B, N, C >= 1, 1 <= M <= 32768, 0 <= offset <= M - N, sx, sy,
+ * cell_w0 finite, flip 0 or 1; anything else is YOLO2_E_ARG before any HIP call.
+ *
+ * yolo2_wbf (Solovyev, Wang, Gabruseva, Image and Vision Computing 2021; per class, unit view weights, conf_type = avg).  Per (image,
+ * class): the candidates are the pooled boxes with conf > threshold (NaN is none), taken by (score descending, pooled index ascending).
+ * A candidate's IoU is computed with every cluster's CURRENT FUSED box (yolo2_nms's operation order, the cluster in the picked box's
+ * place); the best cluster is the one of largest IoU, lowest index among equals.  If there is one and its IoU >= fuse_iou (`>=` as in
+ * yolo2_nms, not the paper's `>`) the candidate joins: Sx0 += s * x0 ... (one multiply, one add), S += s, T += 1, fused box = sums / S.
+ * Otherwise it opens a cluster whose fused box is the candidate's box itself (sums s * x, S = s, T = 1).  A cluster's score is
+ * ((S / T) * min(T, V)) / V.  Per image the clusters are written class ascending, in creation order inside a class, to out_conf [B,R,C]
+ * (the score in the class's column, +0.0f in the others), out_xy_min / out_xy_max [B,R,2]; rows[b] = the number of rows written, and every
+ * row from there up to R is +0.0f.  f32, bit for bit reproducible (tests/tta_ref.py).  `flags` (one int, zeroed by the caller, only ever
+ * OR-ed) receives YOLO2_WBF_FLAG_CANDIDATES: more than YOLO2_WBF_MAX_CANDIDATES candidates in some (image, class); _CLUSTERS: more than
+ * max_per_class clusters in some (image, class) -- such an (image, class) emits nothing; _ROWS: more than R clusters in an image, which
+ * emits its first R.  A caller treats a non-zero word as an error.  Two launches: fuse (one workgroup per (image, class)) and emit (one
+ * per image).  ws: yolo2_wbf_workspace_bytes(B, C, max_per_class) bytes, 16-byte aligned, any content.
+ * B >= 1, 1 <= M <= 32768, C >= 1, threshold >= 0, fuse_iou finite, V >= 1, 1 <= max_per_class <= 1024, R >= 1; anything else is
+ * YOLO2_E_ARG before any HIP call.  Boxes finite with xy_min <= xy_max.  Unit view weights and per class only. */
+#define YOLO2_WBF_MAX_CANDIDATES 4096
+#define YOLO2_WBF_FLAG_CANDIDATES 1
+#define YOLO2_WBF_FLAG_CLUSTERS 2
+#define YOLO2_WBF_FLAG_ROWS 4
+size_t yolo2_wbf_workspace_bytes(int B, int C, int max_per_class);
+int yolo2_tta_gather(const float *conf, const float *xy_min, const float *xy_max, float *out_conf, float *out_xy_min, float *out_xy_max,
+                     int B, int N, int C, int M, int offset, float sx, float sy, float cell_w0, int flip, void *stream);
+int yolo2_wbf(const float *conf, const float *xy_min, const float *xy_max, float *out_conf, float *out_xy_min, float *out_xy_max, int *rows,
+              int *flags, void *ws, int B, int M, int C, int V, int max_per_class, int R, float threshold, float fuse_iou, void *stream);
+
 /* ---- optimizers: train.py:70-80 (TF-1.0 Apply* kernels), flat f32 buffers of n elements ------ */
 int yolo2_adam(float *w, const float *g, float *m, float *v, long n, float alpha, float beta1,
                float beta2, float eps, float gscale, void *stream);   /* alpha = lr*sqrt(1-b2^t)/(1-b1^t) */

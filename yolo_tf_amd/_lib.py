@@ -85,6 +85,8 @@ SIGNATURES = {
     'yolo2_l2_regularizer': [_p, _p, _l, _f, _p, _p],
     'yolo2_nms': [_p, _p, _p, _p, _p, _i, _i, _i, _f, _f, _p],
     'yolo2_soft_nms': [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _p],
+    'yolo2_tta_gather': [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _f, _i, _p],
+    'yolo2_wbf': [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _f, _p],
     'yolo2_adam': [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _p],
     'yolo2_momentum': [_p, _p, _p, _l, _f, _f, _f, _p],
     'yolo2_sgd': [_p, _p, _l, _f, _f, _p],
@@ -152,6 +154,7 @@ QUERIES = {
     'yolo2_image_prep_workspace_bytes': (ctypes.c_size_t, [_i]),
     'yolo2_loss_workspace_bytes': (ctypes.c_size_t, [_i, _i, _i]),
     'yolo2_nms_workspace_bytes': (ctypes.c_size_t, [_i, _i, _i]),
+    'yolo2_wbf_workspace_bytes': (ctypes.c_size_t, [_i, _i, _i]),
     'yolo2_clip_workspace_bytes': (ctypes.c_size_t, [_i]),
     'yolo2_clip_fixed_workspace_bytes': (ctypes.c_size_t, [_i]),
     'yolo2_augment_workspace_bytes': (ctypes.c_size_t, [_i]),

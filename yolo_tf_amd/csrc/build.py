@@ -29,6 +29,7 @@ SOURCES = {
     'yolo1.hip': ['-ffp-contract=off'],
     'nms.hip': ['-ffp-contract=off'],
     'soft_nms.hip': ['-ffp-contract=off'],
+    'tta.hip': ['-ffp-contract=off'],
     'augment.hip': ['-ffp-contract=off'],
     'eval.hip': ['-ffp-contract=off'],
     'eval_coco.hip': ['-ffp-contract=off'],

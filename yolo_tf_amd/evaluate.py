@@ -15,6 +15,7 @@ import torch
 
 from . import ops
 from ._lib import HipKernelError, query
+from .utils.augment import FLIP as AUGMENT_FLIP
 from .utils.augment import AugmentConfig, DeviceInputPipeline
 
 RECORD_DTYPE = np.dtype([('score', '<f4'), ('image', '<i4'), ('box', '<i4'), ('class_flag', '<u4')])      # yolo2_eval_record
@@ -325,17 +326,29 @@ class EvalData(object):
     def batches(self, protocol='voc'):
         for base in range(0, len(self.sizes), self.B):
             n_valid = min(self.B, len(self.sizes) - base)
-            pipe = self.pipe
-            arr = pipe.assemble(list(range(base, base + n_valid)) + [0] * (self.B - n_valid))[0]
-            assert all(a.flags == 0 and (a.crop_x, a.crop_y, a.crop_w, a.crop_h) == (0, 0, a.src_w, a.src_h) for a in arr)
-            params = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).cuda()
-            ops.augment_images(pipe.src, params, pipe.ws, pipe.out, self.B, pipe.H, pipe.W, False)
-            if protocol == 'coco':
-                gt = device_gt_coco(*self.batch_gt_coco(base, n_valid))
-            else:
-                gt = tuple(device_gt(*self.batch_gt(base, n_valid)))
-            self._keep = (params, gt)            # alive until the next batch (asynchronous kernels)
-            yield pipe.out, gt, base, n_valid
+            images, gt = self.batch(base, n_valid, protocol)
+            yield images, gt, base, n_valid
+
+    def batch(self, base, n_valid, protocol='voc', flip=False, with_gt=True):
+        """The images base .. base+n_valid-1 at the current size (padded to B) and their ground truth: one resize launch into the shared
+        batch buffer.  ``flip`` sets the resize kernel's mirror flag (a test-time augmentation view: no extra launch, no copy); the ground truth
+        is never mirrored.  ``with_gt`` False skips the ground truth's upload (-> None)."""
+        pipe = self.pipe
+        arr = pipe.assemble(list(range(base, base + n_valid)) + [0] * (self.B - n_valid))[0]
+        assert all(a.flags == 0 and (a.crop_x, a.crop_y, a.crop_w, a.crop_h) == (0, 0, a.src_w, a.src_h) for a in arr)
+        if flip:
+            for a in arr:
+                a.flags = AUGMENT_FLIP
+        params = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).cuda()
+        ops.augment_images(pipe.src, params, pipe.ws, pipe.out, self.B, pipe.H, pipe.W, False)
+        if not with_gt:
+            gt = None
+        elif protocol == 'coco':
+            gt = device_gt_coco(*self.batch_gt_coco(base, n_valid))
+        else:
+            gt = tuple(device_gt(*self.batch_gt(base, n_valid)))
+        self._keep = (params, gt)            # alive until the next batch (asynchronous kernels)
+        return pipe.out, gt
 
 
 def gt_in_cells(objects, sizes, cell_width, cell_height, difficult=None):
@@ -368,23 +381,63 @@ def device_gt_coco(cls, box, area, flags, first, scale, device='cuda'):
     return (c, b, torch.from_numpy(np.ascontiguousarray(area, np.float32)).to(device), f, o, torch.from_numpy(np.ascontiguousarray(scale, np.float32)).to(device))
 
 
+def records_per_image(N, C, mode, protocol='voc', fused=False, max_dets=100):
+    """The most records one image can append: what ``evaluate`` sizes the record buffer by (times the number of images; the collect
+    entries take at most 2^31 - 1 records).  N boxes of C classes: mode 'detect' one per box, mode 'all' one per (box, class) -- under the
+    COCO protocol at most ``max_dets`` per class.  ``fused``: the N rows come from a test-time augmentation's fusion, where a row IS one
+    (box, class) with a single score, so N rows are N records in either mode."""
+    if fused:
+        return min(N, max_dets * C) if protocol == 'coco' else N
+    if protocol == 'coco':
+        return min(N, max_dets) * C if mode == 'all' else N
+    return N * (C if mode == 'all' else 1)
+
+
 def evaluate(builder, session, data, mode='detect', threshold=0.005, threshold_iou=0.45, iou=0.5, preprocess_mode=0, max_records=None,
-             evaluator=None, on_batch=None, protocol='voc', nms='hard', sigma=0.5):
+             evaluator=None, on_batch=None, protocol='voc', nms='hard', sigma=0.5, tta=None, fuse_iou=0.55, max_per_class=1024):
     """Runs ``session`` (a DetectSession whose batch equals data.B) over ``data`` (an EvalData) and returns Evaluator.result().
     threshold / threshold_iou go to detect() (score threshold and the NMS overlap), iou is the matching threshold.  on_batch(session, gt,
     image_base, n_valid), if given, is called after every detect (tests download the batch there).  protocol 'coco' scores with a
     CocoEvaluator instead (``iou`` is unused: its thresholds are the evaluator's table) and returns CocoEvaluator.result().  nms / sigma
-    choose the suppression of detect(): 'hard' (the reference's), or Soft-NMS 'linear' / 'gaussian'."""
+    choose the suppression of detect(): 'hard' (the reference's), or Soft-NMS 'linear' / 'gaussian'.
+
+    tta: the views (width, height, flip) the session was built with (``DetectSession(tta=...)``; ``data`` must have been built with their
+    sizes as ``input_sizes``): every batch is run at each view -- assembled, run, suppressed and gathered before the next is assembled, since
+    the batch buffer is shared -- and the views' boxes are fused by Weighted Boxes Fusion at the overlap ``fuse_iou`` (at most ``max_per_class``
+    fused boxes per image and class).  The evaluator then sees the fused boxes: N = the session's ``tta_R`` rows in base-grid cells, one row per
+    (fused box, class), so mode 'detect' and mode 'all' count the same detections.  The overflow flags are read once, after the last batch
+    (``session.tta_check``): the loop does not synchronise.  on_batch sees the session after the fusion."""
     assert session.B == data.B, 'the session runs batches of %d, the data yields %d' % (session.B, data.B)
     if protocol not in ('voc', 'coco'):
         raise ValueError("protocol must be 'voc' or 'coco', not %r" % (protocol,))
+    if tta:
+        tta = [(int(w), int(h), bool(f)) for w, h, f in tta]
+        if getattr(session, 'tta', None) != tta:
+            raise ValueError('tta: the session was not built with these views (DetectSession(tta=...))')
     n = len(data.sizes)
+    per_image = records_per_image(session.tta_R if tta else session.N, session.C, mode, protocol, fused=bool(tta))
     if evaluator is None and protocol == 'coco':
-        per_image = min(session.N, 100) * session.C if mode == 'all' else session.N
         evaluator = CocoEvaluator(session.C, max_records or n * per_image, mode=mode, threshold=threshold)
     if evaluator is None:
-        per_image = session.N * (session.C if mode == 'all' else 1)
         evaluator = Evaluator(session.C, max_records or n * per_image, mode=mode, threshold=threshold, iou_threshold=iou)
+    if tta:
+        data.set_size(*tta[0][:2])                        # the ground truth in base-grid cells, once
+        session.tta_begin()
+        for base in range(0, n, data.B):
+            n_valid = min(data.B, n - base)
+            gt = None
+            for v, (w, h, flip) in enumerate(tta):
+                data.pipe.set_size(w, h)                   # (the images' size only: the ground truth stays in the base grid)
+                images, g = data.batch(base, n_valid, protocol, flip=flip, with_gt=v == 0)
+                gt = g if v == 0 else gt
+                session.tta_add(images, (w, h, flip), threshold, threshold_iou, preprocess_mode, nms=nms, sigma=sigma)
+            conf, xy_min, xy_max, _ = session.tta_fuse(threshold, fuse_iou, max_per_class=max_per_class)
+            evaluator.add(conf, xy_min, xy_max, *gt, image_base=base, n_valid=n_valid)
+            if on_batch is not None:
+                on_batch(session, gt, base, n_valid)
+        data.pipe.set_size(*tta[0][:2])
+        session.tta_check()
+        return evaluator.result()
     for images, gt, base, n_valid in data.batches(protocol):
         conf, xy_min, xy_max, _ = session.detect(images, threshold, threshold_iou, preprocess_mode, nms=nms, sigma=sigma)
         evaluator.add(conf, xy_min, xy_max, *gt, image_base=base, n_valid=n_valid)

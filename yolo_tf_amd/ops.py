@@ -343,6 +343,23 @@ def soft_nms(conf, xy_min, xy_max, order, B, N, C, method, thr, thr_iou, sigma=0
     call('yolo2_soft_nms', ptr(conf), ptr(xy_min), ptr(xy_max), ptr(order), B, N, C, int(method), thr, thr_iou, sigma, _stream())
 
 
+def tta_gather(conf, xy_min, xy_max, out_conf, out_xy_min, out_xy_max, B, N, C, M, offset, sx, sy, cell_w0, flip):
+    """yolo2_tta_gather: one view's boxes -> rows offset .. offset+N-1 of the pooled [B,M,.] buffers, in the base grid (sx, sy: f32 scales)."""
+    call('yolo2_tta_gather', ptr(conf), ptr(xy_min), ptr(xy_max), ptr(out_conf), ptr(out_xy_min), ptr(out_xy_max), B, N, C, M, int(offset),
+         float(sx), float(sy), float(cell_w0), int(bool(flip)), _stream())
+
+
+def wbf(conf, xy_min, xy_max, out_conf, out_xy_min, out_xy_max, rows, flags, ws, B, M, C, V, max_per_class, R, thr, fuse_iou):
+    """yolo2_wbf: Weighted Boxes Fusion of the pooled boxes per (image, class); ws: ``workspace_bytes('wbf', B, C, max_per_class)`` bytes;
+    flags (one int32, zeroed by the caller) is OR-ed with the WBF_FLAG_* overflow bits."""
+    call('yolo2_wbf', ptr(conf), ptr(xy_min), ptr(xy_max), ptr(out_conf), ptr(out_xy_min), ptr(out_xy_max), ptr(rows), ptr(flags), ptr(ws),
+         B, M, C, int(V), int(max_per_class), int(R), float(thr), float(fuse_iou), _stream())
+
+
+WBF_MAX_CANDIDATES = 4096                                               # YOLO2_WBF_MAX_CANDIDATES
+WBF_FLAG_CANDIDATES, WBF_FLAG_CLUSTERS, WBF_FLAG_ROWS = 1, 2, 4        # YOLO2_WBF_FLAG_*
+
+
 def adam(w, g, m, v, n, alpha, b1, b2, eps, gscale=1.0):
     call('yolo2_adam', ptr(w), ptr(g), ptr(m), ptr(v), n, alpha, b1, b2, eps, gscale, _stream())
 
@@ -391,7 +408,7 @@ def bn_fold(W, gamma, beta, mean, var, Wf, bias, rows, C, eps):
 
 
 def workspace_bytes(kind, *args):
-    """Caller-owned scratch size of an entry family: 'conv2d', 'bn', 'bias_grad', 'image_prep', 'loss', 'nms', 'clip', 'augment'
+    """Caller-owned scratch size of an entry family: 'conv2d', 'bn', 'bias_grad', 'image_prep', 'loss', 'nms', 'wbf', 'clip', 'augment'
     (include/yolo2_hip.h yolo2_*_workspace_bytes)."""
     return int(_lib.query('yolo2_%s_workspace_bytes' % kind, *args))
 

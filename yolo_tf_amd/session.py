@@ -333,15 +333,35 @@ class TrainSession(object):
 class DetectSession(object):
     """Forward with moving-average BN + decode + batched on-GPU NMS (detect.py:69-80)."""
 
-    def __init__(self, builder, batch_size=1, dtype='bf16', seed=0, calibration=None, sizes=None):
+    def __init__(self, builder, batch_size=1, dtype='bf16', seed=0, calibration=None, sizes=None, tta=None, tta_rows=None):
         """``sizes``: optional list of (width, height) input sizes one set of weights is run at (YOLO9000, table 3); the network is traced at
         each, the buffers are allocated once for the largest, ``set_size`` switches between them and the builder's configured size is
-        selected first.  Not with ``dtype='int8'``: a calibration's engine binds one size."""
+        selected first.  Not with ``dtype='int8'``: a calibration's engine binds one size.
+
+        ``tta``: optional list of views (width, height, flip) for test-time augmentation (``yolo_tf_amd.tta.parse_views``):
+        the first is the base view and must be the builder's configured size, unflipped.  It implies ``sizes`` (the views' sizes); with
+        ``dtype='int8'`` or YOLO (v1) only flip-only views are accepted.  The pooled and fused buffers, the fusion's workspace, ``tta_rows``
+        and ``tta_flags`` are allocated once, here; ``tta_begin`` / ``tta_add`` / ``tta_fuse`` / ``tta_check`` drive them.  None (default):
+        ``session.tta`` is None and nothing is allocated or launched.  ``tta_rows``: rows R of the fused buffers per image, default M (the
+        views' boxes together).  A fused row is one (box, class), so at an evaluation's low threshold, where a box passes in several classes,
+        an image can need up to M * C rows ('evaluation' asks for ``tta.evaluation_rows(M, C)``); too few is reported by ``tta_check``, never silently cut."""
         assert not builder.training
         self.builder = builder
         self.v1 = getattr(builder, 'family', 'yolo2') == 'yolo'
         own = (builder.width, builder.height)
         traced = {own: (builder.graph, builder.model)}
+        self.tta = None
+        if tta:
+            from . import tta as _tta
+            self.tta = _tta.normalise(tta)
+            if self.tta[0][:2] != own:
+                raise ValueError('tta: the base view %dx%d is not the configured input size %dx%d' % (self.tta[0][:2] + own))
+            if not _tta.flip_only(self.tta):
+                if dtype == 'int8':
+                    raise ValueError("dtype='int8' with tta sizes: quantised inference binds one input size (QuantEngine); only flip-only views are accepted")
+                if self.v1:
+                    raise ValueError('tta sizes: the fully connected YOLO (v1) head fixes the input size; only flip-only views are accepted')
+                sizes = list(sizes or []) + [wh for wh in _tta.view_sizes(self.tta) if wh != own]
         if sizes:
             if dtype == 'int8':
                 raise ValueError("dtype='int8' with sizes: quantised inference binds one input size (QuantEngine); run one session per size")
@@ -398,8 +418,77 @@ class DetectSession(object):
         self.nms_ws = torch.zeros(max(ops.workspace_bytes('nms', batch_size, o[0], self.C) for o in self._outputs.values()) // 4,
                                   dtype=torch.int32, device=dev)
         self.async_errors = ops.AsyncErrorPoll()
+        if self.tta:
+            self._tta_allocate(tta_rows)
         self.size = None
         self.set_size(*own)
+
+    def _tta_allocate(self, rows):
+        """The buffers of test-time augmentation, once: pooled [B,M,.] (M = the views' boxes together), fused [B,R,.] with R = ``rows`` or M,
+        the fusion's workspace for min(M, 1024) clusters per class (a class cannot open more clusters than it has
+        candidates, so a larger max_per_class means the same), rows [B] and the flags word."""
+        from . import tta as _tta
+        dev, B, C = self.engine.device, self.B, self.C
+        self._tta_offset, M = [], 0
+        for w, h, _ in self.tta:
+            self._tta_offset.append(M)
+            M += self._outputs[(w, h)][0]
+        if M > _tta.M_LIMIT:
+            raise ValueError('tta: the views hold %d boxes per image together, the fusion takes at most %d' % (M, _tta.M_LIMIT))
+        if rows == 'evaluation':
+            rows = _tta.evaluation_rows(M, C)
+        self.tta_M, self.tta_R = M, M if rows is None else int(rows)
+        if self.tta_R < 1:
+            raise ValueError('tta_rows = %r: the fused buffers hold at least one row' % (rows,))
+        self._tta_cap = min(M, 1024)
+        f32 = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+        self.tta_pooled = (f32(B, M, C), f32(B, M, 2), f32(B, M, 2))
+        self.tta_fused = (f32(B, self.tta_R, C), f32(B, self.tta_R, 2), f32(B, self.tta_R, 2))
+        self.tta_ws = torch.zeros(ops.workspace_bytes('wbf', B, C, self._tta_cap), dtype=torch.uint8, device=dev)
+        self.tta_rows = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.tta_flags = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def tta_begin(self):
+        """Before the first batch of a run of ``tta_add`` / ``tta_fuse``: zeroes the overflow flags (``tta_check`` reads them)."""
+        self.tta_flags.zero_()
+
+    def tta_add(self, images, view, threshold=0.3, threshold_iou=0.4, preprocess_mode=0, nms='hard', sigma=0.5):
+        """One view of the batch: ``set_size``, ``run`` (no synchronisation), the view's own NMS in place, and the gather of its boxes into
+        the pooled buffers in base-grid cells.  ``images``: device f32 [B,h,w,3] at the view's size, already mirrored if the view is flipped.
+        Returns this view's (conf, xy_min, xy_max) after NMS (the session's buffers, in the view's cells)."""
+        view = (int(view[0]), int(view[1]), bool(view[2]))
+        v = self.tta.index(view)
+        self.set_size(view[0], view[1])
+        self.run(images, preprocess_mode, check_numerics=False)
+        self.nms(threshold, threshold_iou, nms, sigma)
+        m, m0 = self.model, self.models[self.tta[0][:2]]
+        sx = np.float32(m0.cell_width) / np.float32(m.cell_width)
+        sy = np.float32(m0.cell_height) / np.float32(m.cell_height)
+        ops.tta_gather(self.conf, self.xy_min, self.xy_max, *self.tta_pooled, self.B, self.N, self.C, self.tta_M, self._tta_offset[v],
+                       sx, sy, m0.cell_width, view[2])
+        return self.conf, self.xy_min, self.xy_max
+
+    def tta_fuse(self, threshold=0.3, fuse_iou=0.55, max_per_class=256):
+        """Weighted Boxes Fusion of what the ``tta_add`` calls pooled (every view once).  Returns device tensors (conf [B,R,C], xy_min, xy_max
+        [B,R,2] in base-grid cells, rows [B] int32): rows[b] fused boxes first, +0.0 after them.  The session is back at the base size."""
+        cap = min(int(max_per_class), self._tta_cap)
+        ops.wbf(*self.tta_pooled, *self.tta_fused, self.tta_rows, self.tta_flags, self.tta_ws, self.B, self.tta_M, self.C, len(self.tta), cap,
+                self.tta_R, float(threshold), float(fuse_iou))
+        self.set_size(*self.tta[0][:2])
+        return self.tta_fused + (self.tta_rows,)
+
+    def tta_check(self):
+        """Synchronises, reads the flags the fusions since ``tta_begin`` left and raises RuntimeError naming the cap that overflowed."""
+        flags = int(self.tta_flags.item())
+        if flags:
+            what = []
+            if flags & ops.WBF_FLAG_CANDIDATES:
+                what.append('more than %d candidates above the threshold in one (image, class): raise the threshold' % ops.WBF_MAX_CANDIDATES)
+            if flags & ops.WBF_FLAG_CLUSTERS:
+                what.append('more clusters than max_per_class in one (image, class): raise max_per_class (at most 1024) or the threshold')
+            if flags & ops.WBF_FLAG_ROWS:
+                what.append('more fused boxes than rows in one image')
+            raise RuntimeError('tta: the fusion overflowed (flags %d): %s' % (flags, '; '.join(what)))
 
     def set_size(self, width, height):
         """Input size of the following runs (one of the sizes the session was built with); the variables are shared."""
