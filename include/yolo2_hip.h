@@ -522,8 +522,22 @@ int yolo2_selftest_tr16(short *out, void *stream);
  *   conv plan  out8 = {tile pixels BM, tile filters BN, waves, 16-byte chunks per K row, LDS stages,
  *                      split (0 none, 1 K-sliced + finishing kernel, 2 stream-K), grid x, grid y};  all -1 = first-layer kernel
  *   wgrad plan out8 = {tile channels BC, tile filters BN, waves, taps paired, pixel ranges, XCD-local placement,
- *                      workgroups, direct store (no atomics)};                                      all -1 = first-layer kernel */
+ *                      workgroups, direct store (no atomics)};                                      all -1 = first-layer kernel
+ * The conv plan words are a copy of what the launch rule (csrc/conv_route.hip y2_conv_route) decided for the call; the persistent and tap-fused
+ * families report their own constants there (stages 9 / 18; split bit 8: the BN-backward sums came from the epilogue; tap-fused grid y bits 8..:
+ * the owner cost in use).  yolo2_debug_conv_route gives the same words without a launch. */
 int yolo2_debug_last_conv_plan(int *out8);
+/* host-side route of a yolo2_conv2d* call, computed by the function the launch uses.  Nothing is launched or allocated; with cus > 0 no device is
+ * touched at all (cus <= 0 asks the runtime for the current device's CU count once per process, like a launch).
+ *   mode: 0 plain, 1 bias and / or activation, 2 yolo2_conv2d_bn, 3 yolo2_conv2d_dgrad_bn;  align_bits: 1 = O, 2 = F, 4 = Yprev 16-byte aligned;
+ *   ws_bytes: 0 = no workspace;  cus: compute units (= stream workgroups; <= 0: the process's current value);
+ *   exclude: families / features that step aside -- 1 image layer, 2 conv_c32, 4 conv_c64, 8 conv_d1, 16 tap-fused, 32 its loader / consumer member,
+ *   64 everything stream-K.  Not an explicit snapshot: the process-wide debug setters, the environment knobs and the calling thread's deterministic
+ *   flag are read at the time of the call, as a launch reads them.
+ *   out12 = {the eight conv plan words, partial rows (0: none written), statistics source (0 none, 1 the kernel's epilogue, 2 a column-sum pass over
+ *            the output, 3 the two-step BN-backward reduction), pending (dgrad_bn), family (0 image layer, 1 c32, 2 c64, 3 d1, 4 pp, 5 s4, 6 igemm)} */
+int yolo2_debug_conv_route(int B, int H, int W, int Cp, int ldp, int Nf, int ldo, int ksize, int dtype, int mode, int align_bits, size_t ws_bytes,
+                           int cus, unsigned exclude, int *out12);
 /* measurement hook: launches an empty kernel (bench.py calibrates the overhead of its HIP-event brackets with it) */
 int yolo2_debug_noop(void *stream);
 /* test hook (process-wide): 0 = per-tap 3x3 kernels only; 2 (and any other non-zero value) = the ping-pong tap-fused kernel (csrc/conv_pp.hip) wherever

@@ -1,4 +1,4 @@
-"""How far the forward / data-gradient launch rule (conv_igemm.hip launch_conv) is from the best forced alternative, per layer shape: runs
+"""How far the forward / data-gradient launch rule (conv_route.hip y2_conv_route) is from the best forced alternative, per layer shape: runs
 scripts/pp_sweep.py for every (batch, input size) of CASES and prints per-tap | RULE | forced stream-K | forced whole tiles with the regret
 RULE / best - 1.  usage: [CASES=8:320,8:480,8:608,4:416,8:416,16:416,32:416] python scripts/launch_rule_regret.py   (one gpurun call)"""
 import os, re, subprocess, sys

@@ -138,6 +138,7 @@ QUERIES = {
     'yolo2_get_stream_workgroups': (_i, []),
     'yolo2_bn_fin_supported': (_i, [_i, _i, _i]),
     'yolo2_debug_last_conv_plan': (_i, [ctypes.POINTER(_i)]),
+    'yolo2_debug_conv_route': (_i, [_i] * 11 + [ctypes.c_size_t, _i, ctypes.c_uint, ctypes.POINTER(_i)]),
     'yolo2_debug_set_igemm_tap': (_i, [_i]),
     'yolo2_debug_set_pp': (_i, [_i, _i, _i, _i]),
     'yolo2_debug_set_pp_cost': (_i, [_i]),

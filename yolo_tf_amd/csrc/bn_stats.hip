@@ -61,17 +61,18 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T *__restrict__ X, in
 
 // Fallback producer of the convolution epilogue's partial format ([2][Y2_BN_PART_ROWS][C], zero on entry): used for the
 // layers whose convolution cannot produce the sums itself (first-layer direct kernel, K-sliced grids).
-int y2_colsum_into(const void *Y, int ld, long M, int C, const float *shift, float *part, int dtype, hipStream_t st, int *rows_used) {
+int y2_colsum_rows(long M, int C, int dtype) {
     const int vec = dtype == YOLO2_BF16 ? 8 : 4;
-    Y2_CHECK_ARG(C % vec == 0 && C / vec <= 256 && ld == C);
     int nb = colsum_grid(M, C, vec);
     if (nb > Y2_BN_PART_ROWS) nb = Y2_BN_PART_ROWS;
-    {   // no more rows than a consumer that finalises them in its prologue reads (bn.hip fin_shape_ok: rows x slice x 8 bytes <= 128 KB)
-        const int tpr = C / vec, lpr = tpr < 16 ? tpr : 16;
-        const long lim = (128L << 10) / ((long)lpr * vec * 8);
-        if (nb > lim) nb = (int)lim;
-    }
-    if (rows_used) *rows_used = nb;
+    // no more rows than a consumer that finalises them in its prologue reads (bn.hip fin_shape_ok: rows x slice x 8 bytes <= 128 KB)
+    const long lim = (128L << 10) / ((long)(C / vec < 16 ? C / vec : 16) * vec * 8);
+    return nb > lim ? (int)lim : nb;
+}
+int y2_colsum_into(const void *Y, int ld, long M, int C, const float *shift, float *part, int dtype, hipStream_t st) {
+    const int vec = dtype == YOLO2_BF16 ? 8 : 4;
+    Y2_CHECK_ARG(C % vec == 0 && C / vec <= 256 && ld == C);
+    const int nb = y2_colsum_rows(M, C, dtype);
     Y2_DISPATCH_DTYPE(dtype, colsum_kernel<T, 2><<<nb, 256, 0, st>>>((const T *)Y, ld, M, C, part, shift, Y2_BN_PART_ROWS));
     Y2_CHECK_LAUNCH();
     return YOLO2_OK;

@@ -9,6 +9,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = {
+    'conv_route.hip': [],
     'conv_igemm.hip': [],
     'conv_pp.hip': [],
     'conv_s4.hip': [],

@@ -18,6 +18,7 @@ typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 void yolo2_set_error(const char *fmt, ...);
 int y2_deterministic();      // the calling thread's deterministic mode (yolo2_set_deterministic)
+int y2_device_cus();         // compute units of the device that was current at the first call (256 when there is none): the ONE cached copy
 
 #if defined(__HIP_DEVICE_COMPILE__)
 // ds_read_b64_tr_b16 through inline asm.  The builtin form is a compiler-visible LDS read: while an LDS-DMA (buffer_load ... lds)
@@ -118,7 +119,8 @@ int y2_first_layer_wgrad_blocks(int B, int H, int W);
 #define Y2_BN_PART_ROWS YOLO2_BN_PART_ROWS
 // the 2 x Y2_BN_PART_ROWS partial rows of a fused BN-backward data gradient -> dgamma (plane 0), dbeta (plane 1); rows zeroed again
 int y2_bn_part_to_grads(float *part, int C, float *dgamma, float *dbeta, hipStream_t st);
-int y2_colsum_into(const void *Y, int ld, long M, int C, const float *shift, float *part, int dtype, hipStream_t st, int *rows_used = nullptr);
+int y2_colsum_rows(long M, int C, int dtype);      // partial rows y2_colsum_into writes (= its workgroups)
+int y2_colsum_into(const void *Y, int ld, long M, int C, const float *shift, float *part, int dtype, hipStream_t st);
 
 #define Y2_CHECK_ARG(cond)                                                          \
     do {                                                                            \

@@ -371,12 +371,12 @@ extern "C" int yolo2_debug_c32_stamps(void *host_out) { return (int)hipMemcpyFro
 
 bool y2_c32_shape(int Cp, int ldp, int Nf, int ldo, int ksize, int dtype) { return dtype == YOLO2_BF16 && ksize == 3 && Cp == 32 && ldp == 32 && Nf == 64 && ldo == 64; }
 
-// -> 0 launched (*rows = partial rows touched when bn_part), 1 the shape does not fit this kernel's LDS plan (caller takes the generic kernels)
-int y2_c32_fwd(const void *P, const void *F, void *O, int B, int H, int W, const float *bias, float alpha, const float *bn_shift, float *bn_part,
-               int cus, int *rows, hipStream_t st) {
+// geometry of a launch on `cus` workgroups (conv_shared.h; `geo`: the kernel's form of it, for the launcher); grid 0: the ring of pixel rows does
+// not fit LDS (or the padded index is too long)
+Y2PersistentPlan y2_c32_plan(int B, int H, int W, int cus, C32Geo *geo) {
+    C32Geo local, &g = geo ? *geo : local;
     const long Mp = (long)B * (H + 1) * (W + 1);
-    if (Mp + 2 * C32_TP >= (1L << 24) || H < 1 || W < 1 || cus < 1) return 1;
-    C32Geo g;
+    if (Mp + 2 * C32_TP >= (1L << 24) || H < 1 || W < 1 || cus < 1) return Y2PersistentPlan{0, 0, 0};
     g.H = H; g.W = W; g.M = B * H * W; g.Mp = (int)Mp;
     g.L = (int)(((Mp + cus - 1) / cus + C32_TP - 1) / C32_TP) * C32_TP;
     const int grid = (int)((Mp + g.L - 1) / g.L);
@@ -384,7 +384,16 @@ int y2_c32_fwd(const void *P, const void *F, void *O, int B, int H, int W, const
     g.NP0 = (g.HLa + C32_TP + W + 2 + 15) / 16;
     g.RR = (16 * g.NP0 + C32_TP + 63) & ~63;                 // the rows of tile t (from its front halo on) and the new rows of tile t + 1
     const size_t lds = (size_t)C32_FBYTES + (size_t)g.RR * 64 + 256;      // filter image, the ring, 64 shifts
-    if (lds > 160 * 1024) return 1;
+    if (lds > 160 * 1024) return Y2PersistentPlan{0, 0, 0};
+    return Y2PersistentPlan{grid, grid < C32_STAT_ROWS ? grid : C32_STAT_ROWS, lds};
+}
+
+// -> 0 launched, 1 the shape does not fit this kernel's LDS plan or the LDS limit cannot be raised (caller takes the generic kernels)
+int y2_c32_fwd(const void *P, const void *F, void *O, int B, int H, int W, const float *bias, float alpha, const float *bn_shift, float *bn_part,
+               int cus, hipStream_t st) {
+    C32Geo g;
+    const auto [grid, rows, lds] = y2_c32_plan(B, H, W, cus, &g);
+    if (!grid) return 1;
     const int M = g.M;
 #ifdef Y2C32_EXPERIMENTS
     static const int abl = y2_env_int("YOLO2_C32_ABL", 0);      // timing ablations (wrong results): 1 no MFMA loop, 2 no stores, 4 no DMA after the first tile, 8 phase stamps
@@ -409,6 +418,5 @@ int y2_c32_fwd(const void *P, const void *F, void *O, int B, int H, int W, const
     else if (bias || alpha != 1.0f) C32_LAUNCH(2, bias);      // (an activation without a bias: the constants read as zeros)
     else C32_LAUNCH(0, (const float *)nullptr);
 #undef C32_LAUNCH
-    if (rows) *rows = grid < C32_STAT_ROWS ? grid : C32_STAT_ROWS;
     return 0;
 }

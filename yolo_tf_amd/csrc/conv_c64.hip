@@ -517,34 +517,6 @@ __global__ __launch_bounds__(512) void conv_c64_wide_kernel(const bf16 *__restri
     }
 }
 
-// -> 0 launched, 1 the shape does not fit the LDS plan (caller takes the generic kernels)
-static int y2_c64_wide(const void *P, const void *F, void *O, int B, int H, int W, int cus, hipStream_t st) {
-    const long Mp = (long)B * (H + 1) * (W + 1);
-    if (Mp + 2 * C64W_TP >= (1L << 23) || H < 1 || W < 1 || cus < 1) return 1;
-    C64Geo g;
-    g.H = H; g.W = W; g.M = B * H * W; g.Mp = (int)Mp;
-    g.L = (int)(((Mp + cus - 1) / cus + C64W_TP - 1) / C64W_TP) * C64W_TP;
-    const int grid = (int)((Mp + g.L - 1) / g.L);
-    g.HLa = (W + 2 + 7) & ~7;
-    g.NP0 = (g.HLa + C64W_TP + W + 2 + 7) / 8;
-    g.RR = (8 * g.NP0 + C64W_TP + 63) & ~63;
-    g.shl_off = 0;
-    const size_t plane = (size_t)g.RR * 128, lds = 2 * plane + 8 * 4096;
-    // room for a filter round (32 rows at pitch 1168 = 37 pieces) behind the first tile's rows of plane 1
-    if (lds > 160 * 1024 || (plane - (size_t)g.NP0 * 1024) + 8 * 4096 < 37 * 1024) return 1;
-    y2_magic_u32((unsigned)(W + 1), &g.mP, &g.sP);
-    y2_magic_u32((unsigned)(H + 1), &g.mH, &g.sH);
-    static std::atomic<size_t> lds_set[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (lds > lds_set[dev].load(std::memory_order_relaxed)) {
-        if (hipFuncSetAttribute((const void *)conv_c64_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 1;
-        lds_set[dev].store(lds, std::memory_order_relaxed);
-    }
-    conv_c64_wide_kernel<<<grid, 512, lds, st>>>((const bf16 *)P, (unsigned)((size_t)g.M * 128 * 2), (const bf16 *)F, (bf16 *)O, g);
-    return 0;
-}
-
 // 64 -> 128 (the forward of conv2 / conv4) or 64 -> 32 (as the forward convolution the data gradient of conv1 is: dY in, flipped taps in the operand)
 bool y2_c64_shape(int Cp, int ldp, int Nf, int ldo, int ksize, int dtype) {
     if (dtype != YOLO2_BF16 || ksize != 3) return false;
@@ -552,39 +524,56 @@ bool y2_c64_shape(int Cp, int ldp, int Nf, int ldo, int ksize, int dtype) {
     return Cp == 64 && ldp == 64 && ((Nf == 128 && ldo == 128) || (Nf == 32 && ldo == 32));
 }
 
-// -> 0 launched (*rows = partial rows touched when bn_part), 1 the shape does not fit this kernel's LDS plan or its 32-filter form has no such epilogue
-// (caller takes the generic kernels)
-int y2_c64_fwd(const void *P, const void *F, void *O, int B, int H, int W, int Nf, const float *bias, float alpha, const float *bn_shift, float *bn_part,
-               int cus, int *rows, hipStream_t st) {
-    if (Nf == 64) {      // 128-channel input (y2_c64_shape): plain stores only
-        if (bn_part || bias || alpha != 1.0f) return 1;
-        if (rows) *rows = 0;      // (no statistics)
-        return y2_c64_wide(P, F, O, B, H, W, cus, st);
-    }
+// geometry of a launch on `cus` workgroups (conv_shared.h; `geo`: the kernel's form of it, for the launcher); grid 0: the shape does not fit the
+// LDS plan, or an epilogue is asked of the 64- / 32-filter forms (y2_c64_shape), which store plainly
+Y2PersistentPlan y2_c64_plan(int B, int H, int W, int Nf, bool epilogue, int cus, C64Geo *geo) {
+    C64Geo local, &g = geo ? *geo : local;
+    const bool wide = Nf == 64, narrow = Nf == 32;      // wide: 128-channel input (conv_c64_wide_kernel)
+    const int TP = wide ? C64W_TP : C64_TP, gran = wide ? C64W_TP : narrow ? 256 : 128;
     const long Mp = (long)B * (H + 1) * (W + 1);
-    if (Mp + 2 * C64_TP >= (1L << 23) || H < 1 || W < 1 || cus < 1) return 1;
-    const bool narrow = Nf == 32;
-    if (narrow && (bn_part || bias || alpha != 1.0f)) return 1;
-    C64Geo g;
+    if ((Nf != 128 && epilogue) || Mp + 2 * TP >= (1L << 23) || H < 1 || W < 1 || cus < 1) return Y2PersistentPlan{0, 0, 0};
     g.H = H; g.W = W; g.M = B * H * W; g.Mp = (int)Mp;
-    const int gran = narrow ? 256 : 128;
     g.L = (int)(((Mp + cus - 1) / cus + gran - 1) / gran) * gran;
     const int grid = (int)((Mp + g.L - 1) / g.L);
     g.HLa = (W + 2 + 7) & ~7;
-    g.NP0 = (g.HLa + C64_TP + W + 2 + 7) / 8;
-    g.RR = (8 * g.NP0 + C64_TP + 63) & ~63;                  // the rows of tile t (from its front halo on) and the new rows of tile t + 1
-    const size_t fround = (size_t)(narrow ? 32 : 64) * C64_FPITCH;
+    g.NP0 = (g.HLa + TP + W + 2 + 7) / 8;
+    g.RR = (8 * g.NP0 + TP + 63) & ~63;                      // the rows of tile t (from its front halo on) and the new rows of tile t + 1
     size_t lds = (size_t)g.RR * 128;
-    if (lds < (size_t)g.NP0 * 1024 + (fround + 1023) / 1024 * 1024) lds = (size_t)g.NP0 * 1024 + (fround + 1023) / 1024 * 1024;      // ... and room for a filter round behind the first tile's rows
-    g.shl_off = (int)lds;
-    lds += 512;                                              // 128 shifts
-    if (lds > 160 * 1024) return 1;
+    if (wide) {      // two planes; room for a filter round (32 rows at pitch 1168 = 37 pieces) behind the first tile's rows of plane 1
+        g.shl_off = 0;
+        if ((lds - (size_t)g.NP0 * 1024) + 8 * 4096 < 37 * 1024) return Y2PersistentPlan{0, 0, 0};
+        lds = 2 * lds + 8 * 4096;
+    } else {
+        const size_t fround = ((size_t)(narrow ? 32 : 64) * C64_FPITCH + 1023) / 1024 * 1024;
+        if (lds < (size_t)g.NP0 * 1024 + fround) lds = (size_t)g.NP0 * 1024 + fround;      // ... and room for a filter round behind the first tile's rows
+        g.shl_off = (int)lds;
+        lds += 512;                                          // 128 shifts
+    }
+    if (lds > 160 * 1024) return Y2PersistentPlan{0, 0, 0};
+    return Y2PersistentPlan{grid, wide ? 0 : grid < C64_STAT_ROWS ? grid : C64_STAT_ROWS, lds};      // (the wide form: no statistics)
+}
+
+// -> 0 launched, 1 y2_c64_plan does not take the call or the LDS limit cannot be raised (caller takes the generic kernels)
+int y2_c64_fwd(const void *P, const void *F, void *O, int B, int H, int W, int Nf, const float *bias, float alpha, const float *bn_shift, float *bn_part,
+               int cus, hipStream_t st) {
+    C64Geo g;
+    const auto [grid, rows, lds] = y2_c64_plan(B, H, W, Nf, bn_part || bias || alpha != 1.0f, cus, &g);
+    if (!grid) return 1;
+    const bool narrow = Nf == 32;
     y2_magic_u32((unsigned)(W + 1), &g.mP, &g.sP);
     y2_magic_u32((unsigned)(H + 1), &g.mH, &g.sH);
     const unsigned x_bytes = (unsigned)((size_t)g.M * 64 * 2);
-    static std::atomic<size_t> lds_set[4][64];
+    static std::atomic<size_t> lds_set[5][64];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    if (Nf == 64) {      // 128-channel input
+        if (lds > lds_set[4][dev].load(std::memory_order_relaxed)) {
+            if (hipFuncSetAttribute((const void *)conv_c64_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 1;
+            lds_set[4][dev].store(lds, std::memory_order_relaxed);
+        }
+        conv_c64_wide_kernel<<<grid, 512, lds, st>>>((const bf16 *)P, (unsigned)((size_t)g.M * 128 * 2), (const bf16 *)F, (bf16 *)O, g);
+        return 0;
+    }
 #define C64_LAUNCH(SLOT, MODEv, NFGv, vecp)                                                                                                  \
     do {                                                                                                                                     \
         if (lds > lds_set[SLOT][dev].load(std::memory_order_relaxed)) {                                                                      \
@@ -598,6 +587,5 @@ int y2_c64_fwd(const void *P, const void *F, void *O, int B, int H, int W, int N
     else if (bias || alpha != 1.0f) C64_LAUNCH(2, 2, 4, bias);      // (an activation without a bias: the constants read as zeros)
     else C64_LAUNCH(0, 0, 4, (const float *)nullptr);
 #undef C64_LAUNCH
-    if (rows) *rows = grid < C64_STAT_ROWS ? grid : C64_STAT_ROWS;
     return 0;
 }

@@ -150,13 +150,16 @@ __global__ __launch_bounds__(512) void conv_d1_dgrad_bn_kernel(
 bool y2_d1_shape(int Cp, int ldp, int Nf, int ldo, int ksize, int dtype, long M) {
     return dtype == YOLO2_BF16 && ksize == 1 && (Cp == 64 || Cp == 128) && ldp == Cp && Nf % D1_BN == 0 && ldo == Nf && M >= 8192;
 }
-// -> 0 launched (*rows = partial rows touched), 1 not taken
-int y2_d1_dgrad_bn(const void *P, const void *F, void *O, long M, int Cp, int Nf, float *bn_part, const Y2BnBwd &bz, int cus, int *rows, hipStream_t st) {
-    if (M >= (1L << 23) || !bn_part || !bz.Y) return 1;
+Y2PersistentPlan y2_d1_plan(long M, int Nf, int cus) {
+    if (M >= (1L << 23)) return Y2PersistentPlan{0, 0, 0};
     const int ntiles = (int)((M + D1_BM - 1) / D1_BM), ngroups = Nf / D1_BN;
-    int gx = cus / ngroups;
-    if (gx < 1) gx = 1;
-    if (gx > ntiles) gx = ntiles;
+    const int gx = cus / ngroups < 1 ? 1 : cus / ngroups > ntiles ? ntiles : cus / ngroups;
+    return Y2PersistentPlan{gx, gx < D1_STAT_ROWS ? gx : D1_STAT_ROWS, 0};
+}
+// -> 0 launched, 1 not taken
+int y2_d1_dgrad_bn(const void *P, const void *F, void *O, long M, int Cp, int Nf, float *bn_part, const Y2BnBwd &bz, int cus, hipStream_t st) {
+    const int ntiles = (int)((M + D1_BM - 1) / D1_BM), ngroups = Nf / D1_BN, gx = y2_d1_plan(M, Nf, cus).grid;
+    if (!gx || !bn_part || !bz.Y) return 1;
     const unsigned p_bytes = (unsigned)((size_t)M * Cp * 2), f_bytes = (unsigned)((size_t)Nf * Cp * 2);
     const dim3 grid(gx, ngroups);
 #define D1_LAUNCH(KCHv, ABLv) conv_d1_dgrad_bn_kernel<KCHv, ABLv><<<grid, 512, 0, st>>>((const bf16 *)P, p_bytes, (const bf16 *)F, f_bytes, (bf16 *)O, (int)M, Nf, ntiles, bn_part, bz)
@@ -169,6 +172,5 @@ int y2_d1_dgrad_bn(const void *P, const void *F, void *O, long M, int Cp, int Nf
     if (Cp == 64) D1_LAUNCH(4, 0); else D1_LAUNCH(8, 0);
 #endif
 #undef D1_LAUNCH
-    if (rows) *rows = gx < D1_STAT_ROWS ? gx : D1_STAT_ROWS;
     return 0;
 }

@@ -29,7 +29,7 @@
 //     __syncthreads() would drain every DMA in flight).
 //   * A = pixels (rows), B = filters (cols): the 32x32 accumulator layout puts 32 consecutive output
 //     channels of one pixel in 32 consecutive lanes -> 64 B (bf16) / 128 B (f32) store segments.
-//   * Shapes (chosen per layer from measurements, launch_conv below): 128x128 tile, 8 waves, 128-byte K rows on a 2-stage
+//   * Shapes (chosen per layer from measurements: conv_route.hip y2_conv_route): 128x128 tile, 8 waves, 128-byte K rows on a 2-stage
 //     ring (64 KiB: two workgroups per CU, 8 MFMAs per wave between barriers) for full grids; 64-byte rows / 3 stages
 //     when the channel count is not a multiple of 64; 64- and 32-filter tiles for the narrow layers.
 //   * Under-filled grids (13x13 / 26x26 stages at batch 16: 88-176 tiles for 256 CUs) run stream-K: one workgroup per CU,
@@ -45,14 +45,16 @@
 //     ROTATED order so that the ~32 workgroups of an XCD read the same bytes of a filter slab (7 MB > the 4 MB L2) at the same
 //     time: 3.6x less fabric traffic on the 3072-channel layer (profiles/r03_l2_stationary_ab.md; the time moved 1.8 %: issue-bound).
 //   * Statistics rows: a producer leaves one partial row per (pixel tile, wave row) while that is no more than the consumer's
-//     prologue reads (y2_stat_rows_limit: 128 rows for >= 128 bf16 channels), else it wraps around 16-128 rows with f32 atomics; the
+//     prologue reads (conv_route.hip set_stat_rows: 128 rows for >= 128 bf16 channels), else it wraps around 16-128 rows with f32 atomics; the
 //     kernel that consumes the moments finishes them (bn.hip *_fin kernels) -- no finalisation launch.
 //   * blockIdx -> tile: filter tile fastest (the blocks of XCD b%8 keep one filter slab in their L2), or,
 //     when the filter operand is small, one contiguous run of M tiles per XCD (halo rows shared in L2).
 #include "common.h"
 #include "conv_shared.h"
 #include "conv_epilogue.h"
+#include "conv_igemm_table.h"
 #include <stdlib.h>
+#include <string.h>
 #include <atomic>
 #include <mutex>
 #include <type_traits>
@@ -523,21 +525,6 @@ __global__ void splitk_finish_kernel(const float *__restrict__ acc, const float 
     }
 }
 
-struct Tune { int target_blocks; int wide; int remap; int stream; int cus; int stream_max_tiles; int bm256; };
-static const Tune &tune() {   // shape-selection constants (each the measured best: profiles/r01_igemm_*.txt, r03_igemm_variant_sweep.txt); two run-time switches remain
-    static Tune t = [] {
-        Tune v{352, 1, -1, 1, 256, 255, 1};   // K slicing only for grids below half the chip (see choose_ksplit)
-        v.stream = y2_env_int("YOLO2_IGEMM_STREAM", v.stream);       // 0: no stream-K anywhere (A/B, debugging a hand-off)
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            v.cus = prop.multiProcessorCount;
-        v.cus = y2_env_int("YOLO2_IGEMM_STREAM_WGS", v.cus);      // workgroups of a stream-K launch (default: one per CU; yolo2_set_stream_workgroups at run time)
-        v.stream_max_tiles = 3 * v.cus;
-        return v;
-    }();
-    return t;
-}
 // Stream-K hand-off flags: Y2_STREAM_FLAG_SETS sets of Y2_STREAM_FLAG_WORDS words per device, allocated and zeroed once; a
 // launch takes the next set round-robin (launches on different streams may overlap) and leaves it zero (every flag is
 // cleared by the one workgroup that waits for it), so no per-launch memset node is needed (16 of them cost 83 us a step).
@@ -549,6 +536,7 @@ static unsigned *g_flag_pool[64] = {nullptr};
 static unsigned g_flag_counter[64] = {0};
 static std::atomic<unsigned> g_sk_wait_ticks{0};       // 0 = Y2_SK_DEFAULT_WAIT_TICKS (tests shorten it: yolo2_debug_set_streamk_wait_us)
 static std::atomic<int> g_sk_unclamped{0};             // tests only: lets a forced grid exceed the number of K steps (the partition bug the wait bound exists for)
+int y2_sk_unclamped() { return g_sk_unclamped.load(std::memory_order_relaxed); }
 __global__ void async_error_gather_kernel(const unsigned *__restrict__ pool, unsigned *__restrict__ host_words) {
     if (threadIdx.x < Y2_STREAM_FLAG_SETS)
         host_words[threadIdx.x] = __hip_atomic_load(pool + (size_t)threadIdx.x * Y2_STREAM_FLAG_STRIDE + Y2_STREAM_FLAG_WORDS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -564,7 +552,7 @@ static unsigned *ensure_pool_locked(int dev) {
     }
     return g_flag_pool[dev];
 }
-static unsigned *stream_flags() {
+unsigned *y2_stream_flags() {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
     std::lock_guard<std::mutex> lock(g_flag_mutex);
@@ -654,465 +642,35 @@ extern "C" int yolo2_shutdown(void) {
     return YOLO2_OK;
 }
 
-// number of K slices: when the M x N tile grid alone cannot fill 256 CUs with ~2-3 resident workgroups
-// each, slice K so that it does, keeping >= 8 K tiles per slice
-static int choose_ksplit(int tiles, int nk, int target) {
-    // measured (profiles/): pays for the 88-tile data gradients; elsewhere atomics + the finishing pass cost more than
-    // the 8-wave / wide-K variants gain
-    if (target <= 0 || nk < 128 || tiles > 128) return 1;
-    int ks = (target + tiles - 1) / tiles;
-    int max_ks = nk / 8;
-    if (ks > max_ks) ks = max_ks;
-    return ks < 1 ? 1 : ks;
+// The lines of conv_igemm_table.h.  Which line a shape gets is conv_route.hip's business (y2_conv_route).
+template <typename T, int BM, int BN, int WGN, int NS, int KS, int SPLIT, bool CT, int CH, int NW, bool BW>
+static void igemm_launch(int grid_x, int grid_y, const Y2IgemmArgs &a, hipStream_t st) {
+    static_assert(!BW || (Y2IgemmPlan<T, BM, BN, WGN, NS, CH, NW>::WIDE_FITS && SPLIT != 1 && !CT), "a BN-backward line no route can name");
+    conv_igemm_kernel<T, BN, WGN, NS, KS, SPLIT, CT, CH, NW, BM, BW><<<dim3(grid_x, grid_y), NW * 64, 0, st>>>(
+        (const T *)a.P, a.p_bytes, (const T *)a.F, a.f_bytes, a.bias, (T *)a.O, a.ws, a.H, a.W, a.Cp, a.ldp, a.Nf, a.ldo, a.M, a.NT, a.remap, a.bn_shift,
+        a.bn_part, a.sk_flags, a.act_alpha, a.wide_store, a.bz);
 }
-
-// the plan of the calling thread's most recent launch (yolo2_debug_last_conv_plan): tests assert that the variant they
-// mean to check is the one that ran, since the choice is shape-driven
-static thread_local int g_last_plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-// Partial rows a statistics-producing launch touches (yolo2_last_bn_part_rows): what the consumer's prologue has to sum.  Up to
-// Y2_BN_PART_ROWS (pixel tile, wave row) pairs get a row each (plain stores, one writer per element); larger grids wrap around
-// R rows with f32 atomic adds, R chosen for <= ~170 adds per address (the 104x104 layer; 20-90 elsewhere) and <= 128 rows to read.
-static thread_local int g_last_stat_rows = Y2_BN_PART_ROWS;
-// most rows the consumer's prologue accepts for Nf channels (bn.hip fin_shape_ok: rows x slice x 8 bytes <= 128 KB), <= 256
-static int y2_stat_rows_limit(int Nf, int vec) {
-    int lpr = Nf / vec;
-    if (lpr > 16) lpr = 16;
-    if (lpr < 1) lpr = 1;
-    const long lim = (128L << 10) / ((long)lpr * vec * 8);
-    return lim > Y2_BN_PART_ROWS ? Y2_BN_PART_ROWS : (int)lim;
+#define Y2_LINE(T, DT, BM, BN, WGN, NS, KS, SPLIT, CT, CH, NW, BW)                                                                        \
+    {{DT, BM, BN, WGN, NS, KS, SPLIT, CT, CH, NW, BW}, Y2IgemmPlan<T, BM, BN, WGN, NS, CH, NW>::WIDE_FITS, Y2IgemmPlan<T, BM, BN, WGN, NS, CH, NW>::STAT_ROWS_FWD, \
+     Y2IgemmPlan<T, BM, BN, WGN, NS, CH, NW>::STAT_ROWS_BNBWD, igemm_launch<T, BM, BN, WGN, NS, KS, SPLIT, CT != 0, CH, NW, BW != 0>},
+#define Y2_F32(...) Y2_LINE(float, YOLO2_F32, __VA_ARGS__)
+#define Y2_BF16(...) Y2_LINE(bf16, YOLO2_BF16, __VA_ARGS__)
+#define Y2_TWIN_NONE(...)
+#define Y2_TWIN_BF16(...) Y2_BF16(__VA_ARGS__, 1)
+#define Y2_TWIN_BOTH(...) Y2_F32(__VA_ARGS__, 1) Y2_BF16(__VA_ARGS__, 1)
+#define Y2_KS(BM, BN, WGN, NS, KS, SPLIT, CT, CH, NW, TW) Y2_F32(BM, BN, WGN, NS, KS, SPLIT, CT, CH, NW, 0) Y2_BF16(BM, BN, WGN, NS, KS, SPLIT, CT, CH, NW, 0) Y2_TWIN_##TW(BM, BN, WGN, NS, KS, SPLIT, CT, CH, NW)
+#define Y2_ROW_K3(BM, BN, WGN, NS, ...) Y2_KS(BM, BN, WGN, NS, 3, __VA_ARGS__)
+#define Y2_ROW_K31(BM, BN, WGN, NS, ...) Y2_KS(BM, BN, WGN, NS, 3, __VA_ARGS__) Y2_KS(BM, BN, WGN, NS, 1, __VA_ARGS__)
+#define Y2_ROW(BM, BN, WGN, NS, SPLIT, CT, CH, NW, KSET, TW) Y2_ROW_##KSET(BM, BN, WGN, NS, SPLIT, CT, CH, NW, TW)
+static const Y2IgemmLine g_igemm_lines[] = {Y2_IGEMM_TABLE(Y2_ROW)};
+const Y2IgemmLine *y2_igemm_line(const Y2IgemmKey &key) {
+    for (const Y2IgemmLine &l : g_igemm_lines)
+        if (!memcmp(&l.key, &key, sizeof(key))) return &l;
+    return nullptr;
 }
-static int y2_stat_rows(long wave_rows, int limit) {
-    if (wave_rows <= limit) return (int)wave_rows;         // one row per (pixel tile, wave row): plain stores
-    // (<= ~16 adds per address: same-address f32 atomics serialise at ~0.1 us each -- 42 per address cost the 52 x 52 BN-backward launch 12 us)
-    int r = 16;
-    while (r < 128 && (long)r * 16 < wave_rows) r <<= 1;
-    while (r > limit) r >>= 1;
-    return r;
-}
-// (batch 8, 26x26 stage: 172 unique rows x 512 channels were more than the consumer reads -- those five layers fell back to the
-// separate finalisation launches; they now wrap around 16 rows like the larger grids)
-static Y2BnBwd y2_with_stat_rows(Y2BnBwd bz, long wave_rows, int Nf, int vec) {
-    const int limit = y2_stat_rows_limit(Nf, vec);
-    const int r = y2_stat_rows(wave_rows, limit);
-    g_last_stat_rows = r;
-    bz.stat_mask_inv = wave_rows <= limit ? 0 : (Y2_BN_PART_ROWS - 1) ^ (r - 1);
-    return bz;
-}
-extern "C" int yolo2_last_bn_part_rows(void) { return g_last_stat_rows; }
-#define Y2_IGEMM_ARGS (const T *)P, p_bytes, (const T *)F, f_bytes, bias, (T *)O, ws, H, W, Cp, ldp, Nf, ldo, M, NT, remap, bn_shift
-#define Y2_IGEMM_BM(BMv, BNv, WGNv, NSv, KSv, SPLITv, CTv, CHv, NWv, gridv)                                        \
-    do {                                                                                                           \
-        const dim3 g_ = (gridv);                                                                                   \
-        const int plan_[8] = {BMv, BNv, NWv, CHv, NSv, SPLITv, (int)g_.x, (int)g_.y};                              \
-        for (int i_ = 0; i_ < 8; ++i_) g_last_plan[i_] = plan_[i_];                                                \
-        typedef Y2IgemmPlan<T, BMv, BNv, WGNv, NSv, CHv, NWv> Plan_;      /* the kernel's own LDS / tile plan (conv_shared.h) */ \
-        /* does this instantiation have the fused BN-backward epilogue? */                                         \
-        const bool fusedbw_ = bz.Y && SPLITv != 1 && !CTv && wide_store && Plan_::WIDE_FITS;                       \
-        const Y2BnBwd bz_ = y2_with_stat_rows(bz, (long)cdiv(M, BMv) * (fusedbw_ ? Plan_::STAT_ROWS_BNBWD : Plan_::STAT_ROWS_FWD), Nf, VEC); \
-        if (!bz.Y)                                                                                                 \
-            conv_igemm_kernel<T, BNv, WGNv, NSv, KSv, SPLITv, CTv, CHv, NWv, BMv, false><<<g_, NWv * 64, 0, st>>>(  \
-                Y2_IGEMM_ARGS, bn_part, sk_flags, act_alpha, wide_store, bz_);                                     \
-        else if (fusedbw_)                                                                                         \
-            conv_igemm_kernel<T, BNv, WGNv, NSv, KSv, (SPLITv == 1 ? 0 : SPLITv), false, CHv, NWv, BMv, true><<<g_, NWv * 64, 0, st>>>( \
-                Y2_IGEMM_ARGS, bn_part, sk_flags, act_alpha, wide_store, bz_);                                     \
-        else {      /* this variant has no on-chip tile image to reduce from: the caller runs the two-step form */ \
-            *stats_done = false;                                                                                   \
-            conv_igemm_kernel<T, BNv, WGNv, NSv, KSv, SPLITv, CTv, CHv, NWv, BMv, false><<<g_, NWv * 64, 0, st>>>(  \
-                Y2_IGEMM_ARGS, nullptr, sk_flags, act_alpha, wide_store, Y2BnBwd{nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0}); \
-        }                                                                                                          \
-    } while (0)
-#define Y2_IGEMM(BNv, WGNv, NSv, KSv, SPLITv, CTv, CHv, NWv, gridv) Y2_IGEMM_BM(128, BNv, WGNv, NSv, KSv, SPLITv, CTv, CHv, NWv, gridv)
-// kernel size x channel tail (4-chunk rows only; 8-chunk rows require Cp % (8*VEC) == 0)
-#define Y2_IGEMM_KS_CT(BNv, WGNv, NSv, SPLITv, NWv, gridv)                              \
-    do {                                                                               \
-        if (ksize == 3) {                                                              \
-            if (ctail) Y2_IGEMM(BNv, WGNv, NSv, 3, SPLITv, true, 4, NWv, gridv);       \
-            else Y2_IGEMM(BNv, WGNv, NSv, 3, SPLITv, false, 4, NWv, gridv);            \
-        } else {                                                                       \
-            if (ctail) Y2_IGEMM(BNv, WGNv, NSv, 1, SPLITv, true, 4, NWv, gridv);       \
-            else Y2_IGEMM(BNv, WGNv, NSv, 1, SPLITv, false, 4, NWv, gridv);            \
-        }                                                                              \
-    } while (0)
-#define Y2_IGEMM_KS_WIDE(SPLITv, gridv)                                                 \
-    do {                                                                               \
-        if (ksize == 3) Y2_IGEMM(128, 2, 3, 3, SPLITv, false, 8, 8, gridv);            \
-        else Y2_IGEMM(128, 2, 3, 1, SPLITv, false, 8, 8, gridv);                       \
-    } while (0)
-
-// tap-fused 3x3 variant on/off (default: env YOLO2_IGEMM_TAP, else on); yolo2_debug_set_igemm_tap flips it at run time so that
-// tests can compare both variants on the same inputs
-// 0 = per-tap kernels only, non-zero = the ping-pong tap-fused kernel (conv_pp.hip) where its launch rule admits it (default).  (The round-2
-// tap-fused kernel it replaced -- slower on every layer it took, profiles/r04_pp2_sched_b16.txt column tap-r2 -- is gone.)
-// 3 = the loader / consumer member of the tap-fused family (conv_s4.hip: four computing waves of 128 x 64 + four loader waves), same launch rule
-static std::atomic<int> g_igemm_tap{y2_env_int("YOLO2_IGEMM_TAP", 2)};
-extern "C" int yolo2_debug_set_igemm_tap(int mode) {
-    g_igemm_tap.store(mode == 3 ? 3 : (mode != 0 ? 2 : 0), std::memory_order_relaxed);
-    return YOLO2_OK;
-}
-static std::atomic<int> g_s4_abl{0};      // experiments build of conv_s4.hip: timing ablations / phase stamps (yolo2_debug_set_s4_abl)
-extern "C" int yolo2_debug_set_s4_abl(int abl) {
-    g_s4_abl.store(abl, std::memory_order_relaxed);
-    return YOLO2_OK;
-}
-// ping-pong kernel knobs (A/B runs and tests): grid 0 = by rule, 1 = stream-K (one workgroup per CU), 2 = one workgroup per tile;
-// dmapos 0/1 = DMA pieces at the head of the LOAD phase / inside the MFMA phase; min_steps, min_share = the launch gates below (< 0: keep)
-static std::atomic<int> g_pp_grid{0};
-static std::atomic<int> g_pp_dmapos{y2_env_int("YOLO2_PP_SCHED", 2)};      // conv_pp.hip SCHED (2 = fragment reads, then the DMA pieces)
-static std::atomic<long> g_pp_min_steps{18};
-static std::atomic<long> g_pp_min_share{24};
-static const int g_pp_long_share = y2_env_int("YOLO2_PP_LONG_SHARE", 26);      // (0 = round 4's rule, for the A/B)
-// cost units charged to the owner of a stream-K tile, in K steps (conv_pp.hip "cost-balanced shares"); 0 = equal K-step shares (round 5).  6 = what
-// a second prologue costs a two-segment workgroup: the dominant launches 54.46 -> 53.9 us, the step -12 us, batch 8 / multi-scale equal or better;
-// 8 and more lose again -- the owner then waits for partners that take longer (profiles/r06_pp_cv_sweep.txt, its last block)
-static std::atomic<int> g_pp_cv{y2_env_int("YOLO2_PP_CV", 6)};
-extern "C" int yolo2_debug_set_pp_cost(int cv) {
-    if (cv < 0 || cv > 4096) { yolo2_set_error("yolo2_debug_set_pp_cost: 0 .. 4096 K steps"); return YOLO2_E_ARG; }
-    g_pp_cv.store(cv, std::memory_order_relaxed);
-    return YOLO2_OK;
-}
-extern "C" int yolo2_debug_set_pp(int grid, int dmapos, int min_steps, int min_share) {
-    if (grid != -1) g_pp_grid.store(grid, std::memory_order_relaxed);
-    if (dmapos >= 0) g_pp_dmapos.store(dmapos, std::memory_order_relaxed);
-    if (min_steps >= 0) g_pp_min_steps.store(min_steps, std::memory_order_relaxed);
-    if (min_share >= 0) g_pp_min_share.store(min_share, std::memory_order_relaxed);
-    return YOLO2_OK;
-}
-
-// Stream-K launches take exactly one workgroup per CU.  A process that shares the GPU with persistent kernels of another stream -- an
-// RCCL ring holds one workgroup per channel for the whole collective -- would get a second, mostly idle wave of workgroups on the CUs
-// that are left; yolo2_set_stream_workgroups(n) (data-parallel sessions: CUs - [mi355x] comm_cus) sizes the launches for the CUs that
-// are free.  0 restores the default (all CUs, or YOLO2_IGEMM_STREAM_WGS).  Correctness never depends on the value: owners only wait
-// for parked tails, and a tail is the first thing its workgroup does (deadlock-free under any residency; tests/test_streamk_occupied_gpu.py).
-static std::atomic<int> g_stream_wgs{0};
-extern "C" int yolo2_set_stream_workgroups(int n) {
-    if (n < 0 || n > Y2_STREAM_FLAG_WORDS) { yolo2_set_error("yolo2_set_stream_workgroups: 0 (default) .. %d", Y2_STREAM_FLAG_WORDS); return YOLO2_E_ARG; }
-    g_stream_wgs.store(n, std::memory_order_relaxed);
-    return YOLO2_OK;
-}
-extern "C" int yolo2_get_stream_workgroups(void) {
-    const int n = g_stream_wgs.load(std::memory_order_relaxed);
-    return n > 0 ? n : tune().cus;
-}
-static Tune tune_now() {
-    Tune t = tune();
-    const int n = g_stream_wgs.load(std::memory_order_relaxed);
-    if (n > 0) { t.cus = n; t.stream_max_tiles = 3 * n; }
-    return t;
-}
-
-template <typename T>
-static int launch_conv(const void *P, const void *F, const float *bias, void *O, float *ws, size_t ws_bytes, int B, int H, int W,
-                       int Cp, int ldp, int Nf, int ldo, int ksize, hipStream_t st, const float *bn_shift, float *bn_part, bool *stats_done, float act_alpha,
-                       const Y2BnBwd bz = Y2BnBwd{nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0}) {
-    const int M = B * H * W;
-    const int MT = cdiv(M, 128);
-    constexpr int VEC = 16 / sizeof(T);
-    constexpr int BK = 4 * VEC;
-    const Tune tu = tune_now();
-    const unsigned p_bytes = (unsigned)((size_t)M * ldp * sizeof(T));
-    const unsigned f_bytes = (unsigned)((size_t)Nf * ksize * ksize * Cp * sizeof(T));
-    const bool ctail = (Cp % BK) != 0;
-    unsigned *sk_flags = nullptr;
-    // 16-byte epilogue stores need 16-byte aligned pixel rows, and a partial last chunk may only spill into this tensor's own
-    // padding lanes (written as zeros), never into a neighbouring concat slice
-    const int wide_store = ((uintptr_t)O & 15) == 0 && ldo % VEC == 0 && (Nf % VEC == 0 || ldo < Nf + VEC);
-    // XCD mapping: filter operand small -> contiguous M runs per XCD; else filter tiles pinned per XCD
-    const int remap = tu.remap >= 0 ? tu.remap : (f_bytes <= (3u << 19) ? 1 : 0);
-    const int MT2 = cdiv(M, 256), NT2 = cdiv(Nf, 128);
-    const long nk_wide = (Cp % (8 * VEC) == 0) ? (long)ksize * ksize * (Cp / (8 * VEC)) : 0;
-    // Long reductions on under-filled grids (13x13 stages: 1024+ input channels): 256 x 128 tile, 8 waves of 64 x 64
-    // (half the LDS fragment traffic and 25 % less DMA per flop than 32 x 64 per wave), always stream-K.  Measured
-    // (profiles/r01_igemm_bm256.txt): +23 % on the 3072-channel layer; shorter reductions, fuller grids and grids under
-    // 64 tiles (each tile cut into > 4 parts: the owner's serial fix-up) lose.
-    if constexpr (std::is_same<T, bf16>::value) {
-        const int tap_mode = g_igemm_tap.load(std::memory_order_relaxed);
-        // Ping-pong tap-fused kernel (conv_pp.hip): 3x3 layers on images up to 55 wide whose input is a multiple of 64 channels.  Its
-        // fixed cost per launch (~24 us: prologue, stream-K hand-off, epilogue) against ~0.65 us per K step decides where it wins
-        // (profiles/r04_pp2_*.txt, r04_pp3_*.txt, batch 16 and 8):
-        //   * a tile grid that gives 60-100 % of the CUs one whole tile each: one workgroup per tile, no hand-off (26x26 256->512 forward
-        //     30.8 vs 35.1 us; 52x52 data gradients 31 vs 36.5 us);
-        //   * else stream-K over one workgroup per CU when a workgroup's share is >= 24 K steps and a tile is cut into at most four shares
-        //     (the owner adds its partners' parked partials one after the other: the 13x13 512 -> 1024 forward, 88 tiles, 38.9 vs 41.0 us;
-        //     its data gradient, 44 tiles of the same 24.75 steps per workgroup, 42.4 vs 41.1 us: per-tap; >= 1024-channel 13x13 layers
-        //     55 vs 60-75 us, 126 vs 144-181 us);
-        //   * a data gradient that also reduces the producer's BN-backward sums takes it from 10 steps per workgroup when it has >= 8192
-        //     pixels: the per-tap kernels' form of that epilogue costs 12-30 us there, this one 4-7.
-        if (tap_mode != 0 && ksize == 3 && Cp % 64 == 0 && W <= 55 && Nf > 64 && wide_store && ws && tu.stream &&
-            (long)9 * (Cp / 64) >= g_pp_min_steps.load(std::memory_order_relaxed) && tu.cus <= Y2_STREAM_FLAG_WORDS) {
-            const long tiles_t = (long)MT2 * NT2, units_p = tiles_t * 9 * (Cp / 64);
-            const int gm = g_pp_grid.load(std::memory_order_relaxed);
-            const bool can_stream = (size_t)tu.cus * 256 * 128 * sizeof(float) <= ws_bytes;
-            int grid = 0;
-            if (gm == 1) grid = can_stream ? tu.cus : 0;
-            else if (gm == 2) grid = tiles_t <= Y2_STREAM_FLAG_WORDS ? (int)tiles_t : 0;
-            else if (gm >= 8) grid = (can_stream && gm <= tu.cus) ? gm : 0;                  // explicit workgroup count (sweeps)
-            else if (gm <= -2) grid = (can_stream && tiles_t * -gm <= tu.cus) ? (int)(tiles_t * -gm) : 0;      // -P: every tile cut into exactly P shares
-            else if (tiles_t * 10 >= (long)tu.cus * 6 && tiles_t <= tu.cus) grid = (int)tiles_t;
-            else if (can_stream && ((units_p >= g_pp_min_share.load(std::memory_order_relaxed) * tu.cus && tiles_t * 4 >= tu.cus) ||
-                                    (bz.Y && M >= 8192 && units_p >= 10L * tu.cus) ||
-                                    // long shares (>= 26 steps per workgroup) outweigh a tile cut into 5-8 of them -- batch 8, 48 tiles: conv20
-                                    // forward 79 vs 119 us, conv18 41.2 vs 44.6 (profiles/r04_pp6_b8.txt); the COCO-80 batch-8 step 2.84 -> 2.82 ms
-                                    // (profiles/r05_long_share_b8.txt)
-                                    (g_pp_long_share > 0 && units_p >= (long)g_pp_long_share * tu.cus && tiles_t * 8 >= tu.cus))) grid = tu.cus;
-            // every workgroup of a stream-K launch must hold at least one K step: an owner waits for the flag of EVERY workgroup whose range
-            // lies inside its tile, and one without work never raises it (only a forced grid on a tiny problem gets here: the rule above
-            // asks for >= 10 steps per workgroup)
-            if (grid > units_p && !g_sk_unclamped.load(std::memory_order_relaxed)) grid = (int)units_p;
-            if (grid > 0 && (sk_flags = stream_flags()) != nullptr) {
-                const int plan_[8] = {256, 128, 8, 8, 18, 2, grid, 1};      // "stages" 18: nine taps per halo image, two phases per tap
-                for (int i_ = 0; i_ < 8; ++i_) g_last_plan[i_] = plan_[i_];
-                // partial rows per pixel tile: what the kernel that runs indexes (conv_shared.h)
-                const int tile_rows = tap_mode == 3 ? (bz.Y ? Y2S_STAT_ROWS_BNBWD : Y2S_STAT_ROWS_FWD) : (bz.Y ? Y2P_STAT_ROWS_BNBWD : Y2P_STAT_ROWS_FWD);
-                const Y2BnBwd bz_ = y2_with_stat_rows(bz, (long)MT2 * tile_rows, Nf, VEC);
-                // owner cost of the cost-balanced partition: below half a workgroup's share, so that every workgroup keeps real K steps (an owner
-                // waits for the flag of every workgroup inside its tile); whole-tile grids have no shares to balance
-                int cv = grid == tiles_t ? 0 : g_pp_cv.load(std::memory_order_relaxed);
-                if (cv > units_p / grid / 2) cv = (int)(units_p / grid / 2);
-                g_last_plan[7] = 1 + (cv << 8);      // plan word grid_y: bits 8.. = the owner cost in use
-                if (tap_mode == 3) {
-                    g_last_plan[2] = 4;             // plan word waves: four COMPUTING waves (+ four loaders)
-                    if (y2_conv3x3_s4_launch(P, p_bytes, F, f_bytes, bias, O, ws, H, W, Cp, ldp, Nf, ldo, M, NT2, bn_shift, bn_part, sk_flags, act_alpha, bz_, 1, grid,
-                                             g_s4_abl.load(std::memory_order_relaxed), st) == 0)
-                        return 0;
-                    g_last_plan[2] = 8;
-                }
-                if (y2_conv3x3_pp_launch(P, p_bytes, F, f_bytes, bias, O, ws, H, W, Cp, ldp, Nf, ldo, M, NT2, bn_shift, bn_part, sk_flags, act_alpha, bz_,
-                                         /* K rotation of the stream-K tiles (profiles/r03_l2_stationary_ab.md) */ 1, grid, g_pp_dmapos.load(std::memory_order_relaxed), cv, st) == 0)
-                    return 0;
-            }
-        }
-    }
-    if (Nf > 64 && tu.bm256 && ws && tu.stream && nk_wide >= 128 && MT2 * NT2 >= 64 && MT2 * NT2 <= 3 * tu.cus && tu.cus <= Y2_STREAM_FLAG_WORDS &&
-        (size_t)tu.cus * 256 * 128 * sizeof(float) <= ws_bytes && (sk_flags = stream_flags()) != nullptr) {
-        const int NT = NT2;
-        dim3 grid(tu.cus);
-        if (ksize == 3) Y2_IGEMM_BM(256, 128, 2, 3, 3, 2, false, 8, 8, grid);
-        else Y2_IGEMM_BM(256, 128, 2, 3, 1, 2, false, 8, 8, grid);
-    } else if (Nf > 64) {
-        // 128 x 128 tile, 8 waves (4 x 2, each 32 x 64): two waves per SIMD even when a CU holds a single workgroup.
-        // Grids of <= 256 tiles (the 13x13 / 26x26 stages at batch 16) cannot fill the chip with workgroups, so they
-        // take 128-byte K rows (16 MFMAs per wave between barriers, 96 KiB ring, one workgroup per CU); larger grids
-        // keep 64-byte rows (48 KiB ring, 3 workgroups per CU).  Measured in profiles/r01_igemm_variants.txt.
-        const int NT = cdiv(Nf, 128);
-        // K slicing (grids <= 128 tiles with a long reduction) multiplies the workgroup count, so it pairs with the
-        // narrow variant (3 workgroups per CU); unsliced small grids take the wide one.
-        // (deterministic mode: no K slicing -- its slices meet in f32 atomics; stream-K or the unsplit grid instead)
-        int ks = (ws && !y2_deterministic()) ? choose_ksplit(MT * NT, ksize * ksize * cdiv(Cp, 4 * VEC), tu.target_blocks) : 1;
-        if (ks > 1 && (size_t)M * Nf * sizeof(float) > ws_bytes) ks = 1;
-        const bool wide = tu.wide && ks == 1 && MT * NT <= 256 && Cp % (8 * VEC) == 0;
-        // stream-K: a grid that cannot give every CU a tile (13x13 stages at batch 16: 176 tiles, 88 for the narrower
-        // data gradients) is run by exactly one 8-wave wide-row workgroup per CU, each taking an equal contiguous share
-        // of the flat (tile, K step) space (>= 24 K steps each, else the two partial-tile epilogues dominate).  Grids of
-        // 1-3 tiles per CU gain only when the reduction is long (>= 96 K steps per tile; measured, profiles/)
-        const long units = (long)MT * NT * ksize * ksize * (Cp / (8 * VEC));
-        const bool stream = tu.stream && ws && tu.wide && Cp % (8 * VEC) == 0 && units >= 24L * tu.cus &&
-                            (MT * NT < tu.cus || (MT * NT <= tu.stream_max_tiles && units / (MT * NT) >= 96)) &&
-                            tu.cus <= Y2_STREAM_FLAG_WORDS && (size_t)tu.cus * 128 * 128 * sizeof(float) <= ws_bytes &&
-                            (sk_flags = stream_flags()) != nullptr;
-        if (stream) {
-            dim3 grid(tu.cus);
-            if (ksize == 3) Y2_IGEMM(128, 2, 3, 3, 2, false, 8, 8, grid);
-            else Y2_IGEMM(128, 2, 3, 1, 2, false, 8, 8, grid);
-        } else if (ks > 1) {
-            *stats_done = false;        // partial tiles meet only in the finishing kernel
-            if (hipMemsetAsync(ws, 0, (size_t)M * Nf * sizeof(float), st) != hipSuccess) return 1;
-            dim3 grid(MT * NT, ks);
-            Y2_IGEMM_KS_CT(128, 2, 3, 1, 4, grid);     // 4-wave workgroups: 3 per CU, measured best with slicing
-            long total = (long)M * Nf;
-            int g = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-            splitk_finish_kernel<T><<<g, 256, 0, st>>>(ws, bias, (T *)O, M, Nf, ldo, act_alpha);
-        } else {
-            ws = nullptr;
-            dim3 grid(MT * NT);
-            if (wide) Y2_IGEMM_KS_WIDE(0, grid);
-            else if (Cp % (8 * VEC) == 0) {
-                // full grids with >= 64 channels: 128-byte rows on a 2-stage ring (64 KiB: two workgroups per CU, 8 MFMAs per
-                // wave between barriers instead of 4) -- +8..19 % on the 52x52 / 26x26 stages (profiles/r01_igemm_wide_ns2.txt)
-                if (ksize == 3) Y2_IGEMM(128, 2, 2, 3, 0, false, 8, 8, grid);
-                else Y2_IGEMM(128, 2, 2, 1, 0, false, 8, 8, grid);
-            } else Y2_IGEMM_KS_CT(128, 2, 3, 0, 8, grid);
-        }
-    } else {
-        const int NT = 1;
-        ws = nullptr;
-        dim3 grid(MT);
-        if (ksize == 3 && Cp % (8 * VEC) == 0) {
-            // 3x3 with <= 64 filters and >= 64 channels (the 208x208 / 104x104 data gradients): 128-byte rows, 2-stage ring;
-            // +35 % / +20 % on those two launches; the 1x1 layers measured no gain (profiles/r01_igemm_wide_ns2.txt)
-            if (Nf > 32) Y2_IGEMM(64, 1, 2, 3, 0, false, 8, 4, grid);
-            else Y2_IGEMM(32, 1, 2, 3, 0, false, 8, 4, grid);
-        } else if (Nf > 32) Y2_IGEMM_KS_CT(64, 1, 3, 0, 4, grid);
-        else Y2_IGEMM_KS_CT(32, 1, 3, 0, 4, grid);
-    }
-    return 0;
-}
-
-// Does yolo2_conv2d_dgrad_bn take the producer layer's sums from its own epilogue for this shape?  (The answer the launch rule gives before the variant
-// is known: K-sliced variants still fall back inside the call.)  A/B: YOLO2_FUSE_BN_BWD=0 never; YOLO2_FUSE_BN_BWD_NARROW=1 also the 3x3 data gradients
-// with <= 64 filters on >= 100k pixels -- conv4's at batch 16, where the fused epilogue costs the per-tap kernel 32 us and the separate reduction 19:
-// those run plain by default, and a host that asks first (yolo2_conv2d_dgrad_bn_fuses) schedules reduction + folded apply itself.
-static bool y2_dgrad_bn_fuses(int B, int H, int W, int Nf, int ksize, int dtype) {
-    static const bool fuse = y2_env_int("YOLO2_FUSE_BN_BWD", 1) != 0;
-    static const bool fuse_narrow = y2_env_int("YOLO2_FUSE_BN_BWD_NARROW", 0) != 0;
-    const int vec = dtype == YOLO2_BF16 ? 8 : 4;
-    return fuse && Nf % vec == 0 && (fuse_narrow || !(ksize == 3 && Nf <= 64 && (long)B * H * W >= 100000));
-}
-extern "C" int yolo2_conv2d_dgrad_bn_fuses(int B, int H, int W, int Nf, int ksize, int dtype) {
-    return (B > 0 && H > 0 && W > 0 && Nf > 0 && (dtype == YOLO2_F32 || dtype == YOLO2_BF16) && y2_dgrad_bn_fuses(B, H, W, Nf, ksize, dtype)) ? 1 : 0;
-}
-
-static int conv2d_impl(const void *P, const void *F, const float *bias, void *O, float *ws, size_t ws_bytes, int B, int H,
-                       int W, int Cp, int ldp, int Nf, int ldo, int ksize, int dtype, void *stream, const char *fn,
-                       const float *bn_shift = nullptr, float *bn_part = nullptr, float act_alpha = 1.0f, const Y2BnBwd *bwd = nullptr,
-                       float *dgamma = nullptr, float *dbeta = nullptr, double *red_ws = nullptr, int *pending = nullptr) {
-    if (!(P && F && O) || !(B > 0 && H > 0 && W > 0 && Cp > 0 && Nf > 0) || !(ksize == 1 || ksize == 3) || !(ldp >= Cp && ldo >= Nf)) {
-        yolo2_set_error("%s: argument check failed: pointers / extents / ksize / strides", fn);
-        return YOLO2_E_ARG;
-    }
-    const int vec = dtype == YOLO2_BF16 ? 8 : 4;
-    const size_t esz = dtype == YOLO2_BF16 ? 2 : 4;
-    // the DMA path addresses both operands with 32-bit byte offsets below 2^31
-    // (only the two DMA-read operands; the output is addressed with 64-bit pointers)
-    if ((size_t)B * H * W * (size_t)ldp * esz >= (1ull << 31) || (size_t)Nf * ksize * ksize * Cp * esz >= (1ull << 31) || (size_t)B * H * W >= (1ull << 31) ||
-        Cp % vec || ldp % vec || ((uintptr_t)P & 15) || ((uintptr_t)F & 15)) {
-        yolo2_set_error("%s: argument check failed: operand >= 2 GiB or misaligned (channels must be a multiple of %d)", fn, vec);
-        return YOLO2_E_ARG;
-    }
-    int rc = 0;
-    static const bool first_direct = y2_env_int("YOLO2_FIRST_DIRECT", 1) != 0;
-    if (first_direct && !bias && !bwd && act_alpha == 1.0f && y2_first_layer_shape(Cp, ldp, Nf, ldo, ksize)) {      // image layer: direct kernel (conv_first.hip)
-        if (dtype != YOLO2_F32 && dtype != YOLO2_BF16) { yolo2_set_error("%s: bad dtype %d", fn, dtype); return YOLO2_E_ARG; }
-        y2_first_layer_fwd(P, F, O, B, H, W, dtype, (hipStream_t)stream, bn_shift, bn_part);
-        for (int i = 0; i < 8; ++i) g_last_plan[i] = -1;      // direct first-layer kernel (conv_first.hip)
-        g_last_stat_rows = Y2_BN_PART_ROWS;
-        Y2_CHECK_LAUNCH();
-        return YOLO2_OK;
-    }
-    static const bool c32_direct = y2_env_int("YOLO2_C32", 1) != 0;
-    if (c32_direct && !bwd && y2_c32_shape(Cp, ldp, Nf, ldo, ksize, dtype) && ((uintptr_t)O & 15) == 0) {      // 32 -> 64 channels (conv1): persistent kernel (conv_c32.hip)
-        const Tune tu = tune_now();
-        int rows = 0;
-        if (y2_c32_fwd(P, F, O, B, H, W, bias, act_alpha, bn_shift, bn_part, tu.cus, &rows, (hipStream_t)stream) == 0) {
-            const int plan_[8] = {512, 64, 8, 8, 9, 0, rows, 1};
-            for (int i = 0; i < 8; ++i) g_last_plan[i] = plan_[i];
-            if (bn_part) g_last_stat_rows = rows;
-            Y2_CHECK_LAUNCH();
-            return YOLO2_OK;
-        }
-    }
-    static const bool c64_direct = y2_env_int("YOLO2_C64", 1) != 0;
-    if (c64_direct && !bwd && y2_c64_shape(Cp, ldp, Nf, ldo, ksize, dtype) && ((uintptr_t)O & 15) == 0 && ((uintptr_t)F & 15) == 0) {      // 64 -> 128 channels (conv2 / conv4), 64 -> 32 (conv1's data gradient), 128 -> 64 (conv2 / conv4's data gradients): filters in registers (conv_c64.hip)
-        const Tune tu = tune_now();
-        int rows = 0;
-        if (y2_c64_fwd(P, F, O, B, H, W, Nf, bias, act_alpha, bn_shift, bn_part, tu.cus, &rows, (hipStream_t)stream) == 0) {
-            const int plan_[8] = {Nf == 64 ? 128 : 256, Nf, 8, 8, 9, 0, rows, 1};      // (positions per tile, filters)
-            for (int i = 0; i < 8; ++i) g_last_plan[i] = plan_[i];
-            if (bn_part) g_last_stat_rows = rows;
-            Y2_CHECK_LAUNCH();
-            return YOLO2_OK;
-        }
-    }
-    bool stats_done = true;
-    if (bwd) {      // data gradient + the producer layer's BN/leaky backward sums (yolo2_conv2d_dgrad_bn)
-        static const bool d1_direct = y2_env_int("YOLO2_D1", 1) != 0;
-        const bool can = y2_dgrad_bn_fuses(B, H, W, Nf, ksize, dtype);
-        if (can && d1_direct && bn_part && y2_d1_shape(Cp, ldp, Nf, ldo, ksize, dtype, (long)B * H * W) && ((uintptr_t)O & 15) == 0 && ((uintptr_t)bwd->Y & 15) == 0) {
-            // 1x1 data gradient of the wide early stages (conv3 / conv6): persistent kernel with prefetched y vectors and launch-long sums (conv_d1.hip)
-            const Tune tu = tune_now();
-            int rows = 0;
-            if (y2_d1_dgrad_bn(P, F, O, (long)B * H * W, Cp, Nf, bn_part, *bwd, tu.cus, &rows, (hipStream_t)stream) == 0) {
-                const int plan_[8] = {128, 128, 8, Cp / 8, 1, 0x100, rows, Nf / 128};
-                for (int i = 0; i < 8; ++i) g_last_plan[i] = plan_[i];
-                g_last_stat_rows = rows;
-                Y2_CHECK_LAUNCH();
-                if (pending) *pending = 1;
-                return pending ? YOLO2_OK : y2_bn_part_to_grads(bn_part, Nf, dgamma, dbeta, (hipStream_t)stream);
-            }
-        }
-        if (can) {
-            Y2_DISPATCH_DTYPE(dtype, rc = launch_conv<T>(P, F, bias, O, ws, ws_bytes, B, H, W, Cp, ldp, Nf, ldo, ksize, (hipStream_t)stream,
-                                                         nullptr, bn_part, &stats_done, act_alpha, *bwd));
-        } else {
-            stats_done = false;
-            Y2_DISPATCH_DTYPE(dtype, rc = launch_conv<T>(P, F, bias, O, ws, ws_bytes, B, H, W, Cp, ldp, Nf, ldo, ksize, (hipStream_t)stream,
-                                                         nullptr, nullptr, &stats_done, act_alpha));
-            stats_done = false;
-        }
-        if (rc) { yolo2_set_error("%s: workspace memset failed", fn); return YOLO2_E_LAUNCH; }
-        Y2_CHECK_LAUNCH();
-        g_last_plan[5] |= stats_done ? 0x100 : 0;      // plan word 5 (split mode): bit 8 = the sums came from the epilogue
-        if (pending) *pending = stats_done ? 1 : 0;
-        if (stats_done) return pending ? YOLO2_OK : y2_bn_part_to_grads(bn_part, Nf, dgamma, dbeta, (hipStream_t)stream);
-        return yolo2_bn_leaky_bwd_reduce(O, ldo, bwd->Y, bwd->mean, bwd->var, bwd->gamma, bwd->beta, dgamma, dbeta, red_ws, (long)B * H * W, Nf,
-                                         bwd->eps, bwd->alpha, dtype, stream);
-    }
-    Y2_DISPATCH_DTYPE(dtype, rc = launch_conv<T>(P, F, bias, O, ws, ws_bytes, B, H, W, Cp, ldp, Nf, ldo, ksize, (hipStream_t)stream,
-                                                 bn_shift, bn_part, &stats_done, act_alpha));
-    if (rc) { yolo2_set_error("%s: workspace memset failed", fn); return YOLO2_E_LAUNCH; }
-    Y2_CHECK_LAUNCH();
-    if (bn_part && !stats_done)       // K-sliced path: statistics from a pass over the finished output
-        return y2_colsum_into(O, ldo, (long)B * H * W, Nf, bn_shift, bn_part, dtype, (hipStream_t)stream, &g_last_stat_rows);
-    return YOLO2_OK;
-}
-
-extern "C" size_t yolo2_conv2d_workspace_bytes(int B, int H, int W, int Cp, int Nf, int ksize, int dtype) {
-    // the largest scratch any variant of yolo2_conv2d_ws / _bn / _bias_leaky can use for this shape: one f32 256x128 tile slot
-    // per CU (stream-K) or the f32 [M][Nf] partial-sum image (K-sliced grids); smaller buffers only disable variants
-    if (!(B > 0 && H > 0 && W > 0 && Cp > 0 && Nf > 0) || !(dtype == YOLO2_F32 || dtype == YOLO2_BF16)) return 0;
-    const Tune &tu = tune();
-    const size_t M = (size_t)B * H * W;
-    const int vec = dtype == YOLO2_BF16 ? 8 : 4;
-    size_t need = (size_t)tu.cus * 256 * 128 * sizeof(float);
-    const long tiles = (long)cdiv((long)M, 128) * cdiv(Nf, 128);
-    if (choose_ksplit((int)(tiles > (1 << 30) ? (1 << 30) : tiles), ksize * ksize * cdiv(Cp, 4 * vec), tu.target_blocks) > 1 && M * Nf * sizeof(float) > need)
-        need = M * Nf * sizeof(float);
-    return need;
-}
-
-extern "C" int yolo2_debug_last_conv_plan(int *out8) {
-    if (!out8) return YOLO2_E_ARG;
-    for (int i = 0; i < 8; ++i) out8[i] = g_last_plan[i];
-    return YOLO2_OK;
-}
-
-extern "C" int yolo2_conv2d(const void *P, const void *F, const float *bias, void *O, int B, int H,
-                            int W, int Cp, int ldp, int Nf, int ldo, int ksize, int dtype, void *stream) {
-    return conv2d_impl(P, F, bias, O, nullptr, 0, B, H, W, Cp, ldp, Nf, ldo, ksize, dtype, stream, "yolo2_conv2d");
-}
-
-extern "C" int yolo2_conv2d_bn(const void *P, const void *F, void *O, float *ws, size_t ws_bytes, int B, int H, int W, int Cp, int ldp,
-                               int Nf, int ldo, int ksize, const float *shift, float *bn_part, int dtype, void *stream) {
-    if (!shift || !bn_part || ldo != Nf) {
-        yolo2_set_error("yolo2_conv2d_bn: argument check failed: shift / bn_part NULL or ldo != Nf");
-        return YOLO2_E_ARG;
-    }
-    return conv2d_impl(P, F, nullptr, O, ws, ws_bytes, B, H, W, Cp, ldp, Nf, ldo, ksize, dtype, stream, "yolo2_conv2d_bn", shift, bn_part);
-}
-
-extern "C" int yolo2_conv2d_dgrad_bn(const void *dY, const void *F, void *dX, float *ws, size_t ws_bytes, int B, int H, int W, int Cp, int ldp,
-                                     int Nf, int ldo, int ksize, const void *Yprev, const float *mean, const float *var, const float *gamma,
-                                     const float *beta, float *dgamma, float *dbeta, float *bn_part, double *red_ws, float eps, float alpha,
-                                     int *pending, int dtype, void *stream) {
-    if (!Yprev || !mean || !var || !gamma || !beta || !dgamma || !dbeta || !bn_part || !red_ws) {
-        yolo2_set_error("yolo2_conv2d_dgrad_bn: argument check failed: a producer-layer pointer is NULL");
-        return YOLO2_E_ARG;
-    }
-    const Y2BnBwd bz{Yprev, mean, var, gamma, beta, eps, alpha, 0};
-    return conv2d_impl(dY, F, nullptr, dX, ws, ws_bytes, B, H, W, Cp, ldp, Nf, ldo, ksize, dtype, stream, "yolo2_conv2d_dgrad_bn", nullptr, bn_part, 1.0f,
-                       &bz, dgamma, dbeta, red_ws, pending);
-}
-extern "C" int yolo2_bn_part_to_grads(float *bn_part, int C, float *dgamma, float *dbeta, void *stream) {
-    if (!bn_part || !dgamma || !dbeta || C <= 0) { yolo2_set_error("yolo2_bn_part_to_grads: argument check failed"); return YOLO2_E_ARG; }
-    return y2_bn_part_to_grads(bn_part, C, dgamma, dbeta, (hipStream_t)stream);
-}
-
-extern "C" int yolo2_conv2d_bias_leaky(const void *P, const void *F, const float *bias, void *O, float *ws, size_t ws_bytes, int B, int H, int W,
-                                       int Cp, int ldp, int Nf, int ldo, int ksize, float alpha, int dtype, void *stream) {
-    if (!bias) { yolo2_set_error("yolo2_conv2d_bias_leaky: bias is NULL"); return YOLO2_E_ARG; }
-    return conv2d_impl(P, F, bias, O, ws, ws_bytes, B, H, W, Cp, ldp, Nf, ldo, ksize, dtype, stream, "yolo2_conv2d_bias_leaky", nullptr, nullptr, alpha);
-}
-
-extern "C" int yolo2_conv2d_ws(const void *P, const void *F, const float *bias, void *O, float *ws, size_t ws_bytes, int B,
-                               int H, int W, int Cp, int ldp, int Nf, int ldo, int ksize, int dtype, void *stream) {
-    return conv2d_impl(P, F, bias, O, ws, ws_bytes, B, H, W, Cp, ldp, Nf, ldo, ksize, dtype, stream, "yolo2_conv2d_ws");
+void y2_splitk_finish(const float *acc, const float *bias, void *O, long M, int Nf, int ldo, float act_alpha, int dtype, hipStream_t st) {
+    const long total = M * Nf;
+    const int g = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    if (dtype == YOLO2_BF16) splitk_finish_kernel<bf16><<<g, 256, 0, st>>>(acc, bias, (bf16 *)O, M, Nf, ldo, act_alpha);
+    else splitk_finish_kernel<float><<<g, 256, 0, st>>>(acc, bias, (float *)O, M, Nf, ldo, act_alpha);
 }

@@ -120,7 +120,7 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(
     // parked partials and runs the tile's epilogue, and when its range also holds the tail of the previous tile it pays a second prologue --
     // measured 14 us between the first and the last workgroup to finish with equal K-step shares (profiles/r06_pp_fixed_cost.txt).  The flat space is
     // therefore cut in VIRTUAL units: every tile is nk K steps preceded by `cv` cost units that map to no K step; workgroup w takes the w-th equal
-    // share of the virtual space, so the owner of a tile gets up to cv fewer real K steps.  cv = 0 is round 5's partition.  (launch_conv keeps
+    // share of the virtual space, so the owner of a tile gets up to cv fewer real K steps.  cv = 0 is round 5's partition.  (y2_conv_route keeps
     // cv below half a share: every workgroup of a stream-K launch holds at least one K step.)
     const long vt = (long)nk + cv;
     const long v_total = (long)MT * NT * vt;
@@ -643,7 +643,7 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(
 #endif
 }
 
-// Launch (called by conv_igemm.hip launch_conv once it has decided that the shape takes this kernel): `grid` workgroups share the
+// Launch (called by conv_route.hip y2_conv_launch once the route names this kernel): `grid` workgroups share the
 // flat (tile, K step) space -- one per CU = stream-K; one per tile = whole tiles, no hand-off.
 int y2_conv3x3_pp_launch(const void *P, unsigned p_bytes, const void *F, unsigned f_bytes, const float *bias, void *O, float *ws, int H, int W, int Cp,
                          int ldp, int Nf, int ldo, int M, int NT, const float *bn_shift, float *bn_part, unsigned *sk_flags, float act_alpha,
@@ -656,7 +656,7 @@ int y2_conv3x3_pp_launch(const void *P, unsigned p_bytes, const void *F, unsigne
         if (W <= 27) { if (bwd) Y2P_LAUNCH(true, 312, 5, SCv); else Y2P_LAUNCH(false, 312, 5, SCv); }             \
         else { if (bwd) Y2P_LAUNCH(true, 368, 4, SCv); else Y2P_LAUNCH(false, 368, 4, SCv); }                     \
         return 0;
-    if (W > 55) return 1;      // (the grid <= K steps clamp is launch_conv's: a workgroup without a K step never raises its flag, and its owner's bounded wait gives up)
+    if (!y2_pp_fits(W)) return 1;      // (the grid <= K steps clamp is y2_conv_route's: a workgroup without a K step never raises its flag, and its owner's bounded wait gives up)
     const bool bwd = bz.Y != nullptr || (sched & 32) != 0;      // (+32, measurements only: the BN-backward instantiation without its sums)
 #ifdef Y2P_EXPERIMENTS      // (scripts/pp_experiments_build.sh: the SCHED variants and timing ablations behind profiles/r04_pp*.txt)
 #define Y2P_ABL_CASE(SCv)                                                                                          \

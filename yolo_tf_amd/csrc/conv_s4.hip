@@ -516,7 +516,7 @@ __global__ __launch_bounds__(512) void conv3x3_s4_kernel(
 #endif
 }
 
-// Launch (called by conv_igemm.hip launch_conv once it has decided that the shape takes the tap-fused family and the loader / consumer member of it):
+// Launch (called by conv_route.hip y2_conv_launch once the route names the loader / consumer member of the tap-fused family):
 // `grid` workgroups share the flat (tile, K step) space -- one per CU = stream-K; one per tile = whole tiles, no hand-off.  abl: experiments build only.
 int y2_conv3x3_s4_launch(const void *P, unsigned p_bytes, const void *F, unsigned f_bytes, const float *bias, void *O, float *ws, int H, int W, int Cp,
                          int ldp, int Nf, int ldo, int M, int NT, const float *bn_shift, float *bn_part, unsigned *sk_flags, float act_alpha,
@@ -524,7 +524,7 @@ int y2_conv3x3_s4_launch(const void *P, unsigned p_bytes, const void *F, unsigne
 #define Y2S_LAUNCH(BWDv, HRv, NSBv, ABLv)                                                                                                   \
     conv3x3_s4_kernel<BWDv, HRv, NSBv, ABLv><<<dim3(grid), 512, 0, st>>>((const bf16 *)P, p_bytes, (const bf16 *)F, f_bytes, bias, (bf16 *)O, ws, \
                                                                          H, W, Cp, ldp, Nf, ldo, M, NT, bn_shift, bn_part, sk_flags, act_alpha, bz, k_rotate)
-    if (W > 55) return 1;
+    if (!y2_pp_fits(W)) return 1;
     const bool bwd = bz.Y != nullptr;
 #ifdef Y2S_EXPERIMENTS
 #define Y2S_ABL_CASE(ABLv)                                                                                         \

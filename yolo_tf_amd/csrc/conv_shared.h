@@ -1,4 +1,4 @@
-// Declarations shared by the convolution translation units (conv_igemm.hip, conv_pp.hip, conv_s4.hip, conv_d1.hip, conv_c32.hip, conv_c64.hip,
+// Declarations shared by the convolution translation units (conv_route.hip, conv_igemm.hip, conv_pp.hip, conv_s4.hip, conv_d1.hip, conv_c32.hip, conv_c64.hip,
 // conv_wgrad.hip, conv_wgrad3.hip, conv_wgrad_c32.hip) and the epilogue they share (conv_epilogue.h).
 #pragma once
 #include "common.h"
@@ -12,7 +12,7 @@
 #define Y2_SK_DEFAULT_WAIT_TICKS 200000000u      // 2 s: five orders of magnitude above the longest legitimate wait (a partner's tail segment, < 100 us)
 #if defined(__HIP_DEVICE_COMPILE__)
 // The owner of a stream-K tile waits for the flag of partner workgroup p (called by ONE lane) and clears it.  The wait is bounded: a partition
-// bug (a workgroup without work never raises its flag -- the hang behind launch_conv's grid clamp) or a lost partner must surface as an error,
+// bug (a workgroup without work never raises its flag -- the hang behind y2_conv_route's grid clamp) or a lost partner must surface as an error,
 // not as a hung device.  On a time-out the launch's results are wrong by construction (the owner sums an unfinished slot, and the late partner's
 // flag may be consumed by a later launch of the same flag set): the status word makes yolo2_check_async_errors() return YOLO2_E_LAUNCH and re-zero
 // the pool; hosts bound the exposure by polling it every step without a synchronisation (yolo2_async_error_snapshot: TrainSession.step,
@@ -46,12 +46,12 @@ struct Y2BnBwd {
     float eps, alpha;
     // bits cleared from the partial-row index mask (Y2_BN_PART_ROWS - 1): grids with more (pixel tile, wave row) pairs than rows wrap
     // around R = 256 >> popcount(stat_mask_inv) rows, chosen by the host so that the consumer that finalises the rows in its prologue
-    // (yolo2_bn_leaky_fin & co.) reads few of them while same-address atomic adds stay rare (y2_stat_rows in conv_igemm.hip).  0 = all 256 rows.
+    // (yolo2_bn_leaky_fin & co.) reads few of them while same-address atomic adds stay rare (set_stat_rows in conv_route.hip).  0 = all 256 rows.
     int stat_mask_inv;
 };
 
 // LDS / tile plan of one conv_igemm_kernel instantiation -- the ONE place its sizes are derived: the kernel takes its constants from here, and
-// the host (conv_igemm.hip Y2_IGEMM_BM) counts the partial rows a pixel tile writes from the same struct.
+// the host (conv_route.hip, per line of conv_igemm_table.h) counts the partial rows a pixel tile writes from the same struct.
 template <typename T, int BM, int BN, int WGN, int NSTAGE, int CH, int NW> struct Y2IgemmPlan {
     static constexpr int VEC = 16 / (int)sizeof(T);
     static constexpr int ROWB = CH * 16;          // bytes per tile row (CH 16-byte chunks)
@@ -75,7 +75,10 @@ constexpr int Y2P_STAT_ROWS_FWD = 4, Y2P_STAT_ROWS_BNBWD = 1;
 constexpr int Y2S_STAT_ROWS_FWD = 4, Y2S_STAT_ROWS_BNBWD = 4;
 constexpr int D1_STAT_ROWS = 32;
 
-// conv_pp.hip: ping-pong tap-fused 3x3 kernel (bf16, 256 x 128 tile); returns non-zero when the image is too wide for its halo buffers
+// conv_pp.hip / conv_s4.hip: the tap-fused 3x3 kernels (bf16, 256 x 128 tile) keep a halo image of the input rows in LDS: images up to 55 pixels wide.
+// The ONE place that says so: the launch rule asks before it names the family, the two launchers refuse anything else.
+inline bool y2_pp_fits(int W) { return W <= 55; }
+// conv_pp.hip: ping-pong tap-fused 3x3 kernel; returns non-zero when !y2_pp_fits(W) or `sched` names a schedule this build does not have
 int y2_conv3x3_pp_launch(const void *P, unsigned p_bytes, const void *F, unsigned f_bytes, const float *bias, void *O, float *ws, int H, int W, int Cp,
                          int ldp, int Nf, int ldo, int M, int NT, const float *bn_shift, float *bn_part, unsigned *sk_flags, float act_alpha,
                          const Y2BnBwd &bz, int k_rotate, int grid, int sched, int cv, hipStream_t st);
@@ -103,19 +106,45 @@ bool y2_w32_shape(int Cin, int ldx, int Cout, int ldy, int ksize, int dtype);
 int y2_w32_blocks(int B, int H, int W, int cus);      // workgroups of the launch; 0: not taken
 int y2_w32_wgrad(const void *X, const void *dY, float *dW, int B, int H, int W, int cus, int *blocks, hipStream_t st, float *ws = nullptr);      // ws: one slot per workgroup
 
-// conv_c32.hip: persistent 3x3 forward for 32-channel inputs and 64 filters (Darknet-19 conv1), bf16.  y2_c32_fwd returns non-zero when the image is
-// too wide for its LDS plan (the caller then takes the generic kernels).
-bool y2_c32_shape(int Cp, int ldp, int Nf, int ldo, int ksize, int dtype);
-int y2_c32_fwd(const void *P, const void *F, void *O, int B, int H, int W, const float *bias, float alpha, const float *bn_shift, float *bn_part,
-               int cus, int *rows, hipStream_t st);
+// The persistent families size themselves from the shape and the workgroup count alone.  Each has ONE pure geometry function: the launch rule
+// (conv_route.hip) and the family's own launcher both call it.  grid == 0: the shape is not taken (it does not fit the kernel's LDS plan, or the form
+// that would run has no such epilogue) and the generic kernels run.
+struct Y2PersistentPlan { int grid; int rows; size_t lds; };      // workgroups, partial rows the statistics touch (0: none), dynamic LDS bytes
 
-// conv_c64.hip: persistent 3x3 convolution for 64-channel inputs with 128 filters (Darknet-19 conv2 / conv4 forward) or 32 (conv1's data gradient), bf16,
-// filters held in registers, one ring of pixel rows per workgroup.  y2_c64_fwd returns non-zero when the image is too wide for its LDS plan or the
-// 32-filter form is asked for an epilogue it does not have (the caller then takes the generic kernels).
+// conv_c32.hip: persistent 3x3 forward for 32-channel inputs and 64 filters (Darknet-19 conv1), bf16.  y2_c32_fwd returns non-zero when the plan does
+// not take the shape or the LDS limit cannot be raised (the caller then takes the generic kernels).
+bool y2_c32_shape(int Cp, int ldp, int Nf, int ldo, int ksize, int dtype);
+struct C32Geo;
+Y2PersistentPlan y2_c32_plan(int B, int H, int W, int cus, C32Geo *geo = nullptr);      // (geo: conv_c32.hip's own use)
+int y2_c32_fwd(const void *P, const void *F, void *O, int B, int H, int W, const float *bias, float alpha, const float *bn_shift, float *bn_part,
+               int cus, hipStream_t st);
+
+// conv_c64.hip: persistent 3x3 convolution for 64-channel inputs with 128 filters (Darknet-19 conv2 / conv4 forward) or 32 (conv1's data gradient), and
+// for 128-channel inputs with 64 filters (conv2 / conv4's data gradients), bf16, filters held in registers, one ring of pixel rows per workgroup.
+// `epilogue`: bias, activation or statistics are asked for (the 32- and 64-filter forms store plainly and step aside).
 bool y2_c64_shape(int Cp, int ldp, int Nf, int ldo, int ksize, int dtype);
+struct C64Geo;
+Y2PersistentPlan y2_c64_plan(int B, int H, int W, int Nf, bool epilogue, int cus, C64Geo *geo = nullptr);      // (geo: conv_c64.hip's own use)
 int y2_c64_fwd(const void *P, const void *F, void *O, int B, int H, int W, int Nf, const float *bias, float alpha, const float *bn_shift, float *bn_part,
-               int cus, int *rows, hipStream_t st);
+               int cus, hipStream_t st);
 
 // conv_d1.hip: persistent 1x1 data gradient + the producer layer's BN / leaky backward sums for the wide early stages (conv3 / conv6), bf16
 bool y2_d1_shape(int Cp, int ldp, int Nf, int ldo, int ksize, int dtype, long M);
-int y2_d1_dgrad_bn(const void *P, const void *F, void *O, long M, int Cp, int Nf, float *bn_part, const Y2BnBwd &bz, int cus, int *rows, hipStream_t st);
+Y2PersistentPlan y2_d1_plan(long M, int Nf, int cus);      // (grid = workgroups per column group; Nf / 128 groups)
+int y2_d1_dgrad_bn(const void *P, const void *F, void *O, long M, int Cp, int Nf, float *bn_part, const Y2BnBwd &bz, int cus, hipStream_t st);
+
+// ---- the generic implicit-GEMM kernels (conv_igemm.hip), as the launch rule (conv_route.hip) sees them ----
+struct Y2IgemmKey { int dtype, BM, BN, WGN, stages, KS, split, ctail, chunks, waves, bnbwd; };      // one conv_igemm_kernel instantiation
+struct Y2IgemmArgs {      // the kernel's arguments, in its order
+    const void *P; unsigned p_bytes; const void *F; unsigned f_bytes; const float *bias; void *O; float *ws; int H, W, Cp, ldp, Nf, ldo, M, NT, remap;
+    const float *bn_shift; float *bn_part; unsigned *sk_flags; float act_alpha; int wide_store; Y2BnBwd bz;
+};
+// A line of conv_igemm_table.h: its launcher, and what the rule reads of its LDS / tile plan (Y2IgemmPlan) -- do the wide-store images fit the ring
+// (the BN-backward epilogue reduces from them), the partial rows one pixel tile writes.  y2_igemm_line: nullptr = no such line is built.
+struct Y2IgemmLine { Y2IgemmKey key; bool wide_fits; int rows_fwd, rows_bnbwd; void (*launch)(int grid_x, int grid_y, const Y2IgemmArgs &a, hipStream_t st); };
+const Y2IgemmLine *y2_igemm_line(const Y2IgemmKey &key);
+// K-sliced launches: f32 partial sums [M][Nf] in the workspace -> O (+ bias, activation)
+void y2_splitk_finish(const float *acc, const float *bias, void *O, long M, int Nf, int ldo, float act_alpha, int dtype, hipStream_t st);
+// the next set of stream-K hand-off flags of the current device (round-robin); NULL: no pool (allocation failed)
+unsigned *y2_stream_flags();
+int y2_sk_unclamped();      // tests only (yolo2_debug_set_streamk_wait_us): a forced stream-K grid may exceed the number of K steps

@@ -377,15 +377,6 @@ extern "C" void yolo2_debug_set_wgrad_variant(int v) {
     g_wgrad_variant_raw = v;
     g_wgrad_variant = (v == 1) ? 1 : 0;
 }
-static int wgrad_cus() {
-    static int cached_cus = 0;
-    if (!cached_cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        cached_cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    return cached_cus;
-}
 // plan of the calling thread's most recent launch: {BC, BNN, waves, PAIR, pixel ranges, XCD remap, blocks, direct store}
 static thread_local int g_last_wgrad_plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 extern "C" int yolo2_debug_last_wgrad_plan(int *out8) {
@@ -585,7 +576,7 @@ static int wgrad_launch(const WgradRoute &r, const void *X, const void *dY, floa
         case 0: y2_first_layer_wgrad(X, dY, dW, B, H, W, Cin, dtype, st, ws); break;      // image layer: direct kernel (conv_first.hip)
         case 1: {                                                                       // conv1: all nine taps per workgroup (conv_wgrad_c32.hip)
             int blocks = 0;
-            if (y2_w32_wgrad(X, dY, dW, B, H, W, wgrad_cus(), &blocks, st, ws) == 0) {
+            if (y2_w32_wgrad(X, dY, dW, B, H, W, y2_device_cus(), &blocks, st, ws) == 0) {
                 if (ws && blocks != r.slots) { yolo2_set_error("filter gradient: conv1 kernel launched %d workgroups for %d slots", blocks, r.slots); return YOLO2_E_LAUNCH; }
                 break;
             }
@@ -603,7 +594,7 @@ static int wgrad_launch(const WgradRoute &r, const void *X, const void *dY, floa
 
 extern "C" int yolo2_conv2d_wgrad_accumulates(int B, int H, int W, int Cin, int ldx, int Cout, int ldy, int ksize, int dtype) {
     if (!(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0) || !(ksize == 1 || ksize == 3) || !(dtype == YOLO2_F32 || dtype == YOLO2_BF16)) return 1;
-    const WgradRoute r = wgrad_route(B, H, W, Cin, ldx, Cout, ldy, ksize, dtype, wgrad_cus());
+    const WgradRoute r = wgrad_route(B, H, W, Cin, ldx, Cout, ldy, ksize, dtype, y2_device_cus());
     if (r.family != 0 && g_wgrad_variant != 0) return 1;      // (scalar-gather test hook: be safe, clear)
     return r.slots > 1 ? 1 : 0;                               // several pixel ranges / workgroups add into dW; one stores
 }
@@ -621,7 +612,7 @@ extern "C" int yolo2_conv2d_wgrad(const void *X, const void *dY, float *dW, int 
     Y2_CHECK_ARG(((uintptr_t)X & 15) == 0 && ((uintptr_t)dY & 15) == 0);
     // 32-bit byte offsets below 2^31 on both operands (DMA descriptors)
     Y2_CHECK_ARG((size_t)B * H * W * (size_t)(ldx > ldy ? ldx : ldy) * esz < (1ull << 31));
-    const WgradRoute r = wgrad_route(B, H, W, Cin, ldx, Cout, ldy, ksize, dtype, wgrad_cus());
+    const WgradRoute r = wgrad_route(B, H, W, Cin, ldx, Cout, ldy, ksize, dtype, y2_device_cus());
     return wgrad_launch(r, X, dY, dW, B, H, W, Cin, ldx, Cout, ldy, ksize, dtype, (hipStream_t)stream, nullptr);
 }
 
@@ -637,7 +628,7 @@ static int wgrad_per_tap(const void *X, const void *dY, float *dW, int B, int H,
         // with two or three workgroups per CU the 32-pixel / 3-stage form wins (conv18: 66.5 vs 73.1 us).
         bool use64 = false;
         if (dtype == YOLO2_BF16 && g_wgrad_variant == 0) {
-            const int cached_cus = wgrad_cus();
+            const int cached_cus = y2_device_cus();
             const WgradPlan pl = wgrad_plan(B * H * W, Cin, Cout, ksize, 128, 128, 32);
             use64 = pl.ks == 1 && 2 * pl.blocks <= 3 * cached_cus;
         }
@@ -716,7 +707,7 @@ static void launch_wgrad_reduce(const float *ws, float *dW, long n, long stride,
 
 extern "C" size_t yolo2_conv2d_wgrad_workspace_bytes(int B, int H, int W, int Cin, int ldx, int Cout, int ldy, int ksize, int dtype) {
     if (!wgrad_shape_ok(B, H, W, Cin, ldx, Cout, ldy, ksize, dtype)) return 0;
-    const WgradRoute r = wgrad_route(B, H, W, Cin, ldx, Cout, ldy, ksize, dtype, wgrad_cus());
+    const WgradRoute r = wgrad_route(B, H, W, Cin, ldx, Cout, ldy, ksize, dtype, y2_device_cus());
     return r.slots > 1 ? (size_t)r.slots * (size_t)r.slot_floats * sizeof(float) : 0;
 }
 
@@ -733,7 +724,7 @@ extern "C" int yolo2_conv2d_wgrad_ws(const void *X, const void *dY, float *dW, f
     Y2_CHECK_ARG(X && dY && dW);
     Y2_CHECK_ARG(wgrad_shape_ok(B, H, W, Cin, ldx, Cout, ldy, ksize, dtype));
     Y2_CHECK_ARG(((uintptr_t)X & 15) == 0 && ((uintptr_t)dY & 15) == 0);
-    const WgradRoute r = wgrad_route(B, H, W, Cin, ldx, Cout, ldy, ksize, dtype, wgrad_cus());
+    const WgradRoute r = wgrad_route(B, H, W, Cin, ldx, Cout, ldy, ksize, dtype, y2_device_cus());
     hipStream_t st = (hipStream_t)stream;
     if (r.slots <= 1) return wgrad_launch(r, X, dY, dW, B, H, W, Cin, ldx, Cout, ldy, ksize, dtype, st, nullptr);      // one writer per element already
     const size_t need = (size_t)r.slots * (size_t)r.slot_floats * sizeof(float);

@@ -27,16 +27,6 @@ __global__ __launch_bounds__(256) void ema_kernel(float *__restrict__ ema, const
     for (long k = head + (n4 << 2) + i; k < n; k += stride) ema[k] = ema_one(ema[k], w[k], omd);
 }
 
-static int ema_cus() {
-    static int cached_cus = 0;
-    if (!cached_cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        cached_cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    return cached_cus;
-}
-
 extern "C" int yolo2_ema_update(float *ema, const float *w, long n, float one_minus_decay, void *stream) {
     Y2_CHECK_ARG(ema && w && n > 0 && one_minus_decay >= 0 && one_minus_decay <= 1);
     Y2_CHECK_ARG((((uintptr_t)ema) | ((uintptr_t)w)) % sizeof(float) == 0);
@@ -46,7 +36,7 @@ extern "C" int yolo2_ema_update(float *ema, const float *w, long n, float one_mi
     // memory-bound: eight 256-thread workgroups per CU, the grid-stride loop takes the rest
     long blocks = ((n - head) / 4 + 255) / 256;
     if (blocks < (head + 255) / 256) blocks = (head + 255) / 256;
-    const long cap = 8L * ema_cus();
+    const long cap = 8L * y2_device_cus();
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
     ema_kernel<<<(int)blocks, 256, 0, (hipStream_t)stream>>>(ema, w, n, head, one_minus_decay);

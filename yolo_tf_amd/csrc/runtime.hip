@@ -21,6 +21,15 @@ int y2_deterministic() { return g_deterministic; }
 extern "C" int yolo2_set_deterministic(int on) { g_deterministic = on ? 1 : 0; return YOLO2_OK; }
 extern "C" int yolo2_get_deterministic(void) { return g_deterministic; }
 
+int y2_device_cus() {
+    static const int cus = [] {
+        hipDeviceProp_t prop;
+        int dev = 0;
+        return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+    }();
+    return cus;
+}
+
 // CRC32C (Castagnoli) of a HOST buffer, slicing-by-8: the checksum of TFRecord / TensorBoard event / TF checkpoint files
 // (utils/tfrecord.py, utils/events.py, tf_checkpoint.py); `crc` = value so far (0 to start).  ~1.5 GB/s, against ~1 MB/s in Python.
 extern "C" uint32_t yolo2_crc32c(const void *data, size_t n, uint32_t crc) {

@@ -440,6 +440,25 @@ def last_conv_plan():
     return dict(zip(CONV_PLAN_KEYS, list(out)))
 
 
+CONV_ROUTE_MODES = {'plain': 0, 'bias_act': 1, 'bn': 2, 'dgrad_bn': 3}
+CONV_ROUTE_EXCLUDE = {'first': 1, 'c32': 2, 'c64': 4, 'd1': 8, 'tap': 16, 's4': 32, 'stream': 64}
+CONV_ROUTE_STATS = ('none', 'epilogue', 'colsum', 'two_step')
+CONV_ROUTE_FAMILIES = ('first', 'c32', 'c64', 'd1', 'pp', 's4', 'igemm')
+
+
+def conv_route(B, H, W, Cp, ldp, Nf, ldo, ksize, dtype, mode, ws_bytes, cus=0, exclude=(), align_bits=7):
+    """Host-side route of a conv2d* call (include/yolo2_hip.h yolo2_debug_conv_route; no device): dict(plan, rows, stats, pending, family).
+    ``mode``: a key of CONV_ROUTE_MODES; ``exclude``: keys of CONV_ROUTE_EXCLUDE; ``cus`` 0: the process's current workgroup count."""
+    out = (ctypes.c_int * 12)()
+    mask = 0
+    for name in exclude:
+        mask |= CONV_ROUTE_EXCLUDE[name]
+    rc = _lib.load().yolo2_debug_conv_route(B, H, W, Cp, ldp, Nf, ldo, ksize, dtype_code(dtype), CONV_ROUTE_MODES[mode], align_bits, ws_bytes, cus, mask, out)
+    if rc != 0:
+        raise _lib.HipKernelError('yolo2_debug_conv_route failed (code %d)' % rc)
+    return dict(plan=dict(zip(CONV_PLAN_KEYS, list(out)[:8])), rows=out[8], stats=CONV_ROUTE_STATS[out[9]], pending=out[10], family=CONV_ROUTE_FAMILIES[out[11]])
+
+
 def noop():
     """Empty kernel on the current stream (event-bracket calibration in bench.py)."""
     call('yolo2_debug_noop', _stream())
