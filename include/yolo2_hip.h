@@ -602,6 +602,36 @@ typedef struct yolo2_augment_params {
 int yolo2_augment_images(const unsigned char *src, const yolo2_augment_params *params_device, double *ws, float *out,
                          int B, int H, int W, int any_contrast, void *stream);
 
+/* ---- mosaic and MixUp (new work, the reference has neither): an output image composed of several sources.
+ * tiles [B][L][T] (device), L = 1 or 2 layers of T = 1 .. 4 tiles.  A tile resizes its crop of its source to a VIEW of view_w x view_h
+ * pixels -- the tap rule of yolo2_augment_images with (W, H) = (view_w, view_h), its same-size copy shortcut included -- and places view
+ * pixel (0, 0) at output pixel (origin_x, origin_y), which may be negative or beyond the frame.  The tile supplies the output pixels of
+ * its half-open rectangle [x0, x1) x [y0, y1): at (x, y), with (u, v) = (x - origin_x, y - origin_y), the view's pixel (v, u) where
+ * 0 <= u < view_w and 0 <= v < view_h (with `flip` the view is mirrored first: u -> view_w - 1 - u), and `fill` on all three channels
+ * elsewhere.  A slot with x1 <= x0 or y1 <= y0 is unused.  The caller guarantees that the rectangles of a layer partition the frame
+ * (a pixel no rectangle holds is not written; the part of a rectangle beyond the frame is ignored) and, as for yolo2_augment_images,
+ * that every crop lies inside its source.
+ * mix [B] (device) is the weight lam of layer 0: with L = 2 and mix[b] != 1 the pixel is a * lam + b * (1.0f - lam) of the two layers'
+ * values in f32 without contraction; with mix[b] == 1 layer 1 is not evaluated (its tiles may hold anything).  mix may be NULL when
+ * L = 1.  The chain of yolo2_augment_images then runs on the composite, driven by photo [B] (device; flags and scalars only, the
+ * geometry fields and YOLO2_AUG_FLIP are ignored): brightness, saturation, hue, contrast about the COMPOSITE's per-channel mean (fill
+ * included), noise indexed by the output pixel, grey, clip.  One full-frame tile (L = T = 1, view = frame, origin 0) gives the bits of
+ * yolo2_augment_images.  out: f32 [B, H, W, 3]; ws: yolo2_augment_workspace_bytes(B) bytes when any image takes the contrast branch, any
+ * content.  L, T out of range, a NULL mix with L = 2, a NULL ws with any_contrast, H * W >= 2^30: YOLO2_E_ARG before any HIP call.
+ * 2 x 2 layouts are what the host builds; no rotation or shear, no per-tile colour. */
+typedef struct yolo2_compose_tile {
+    long long src_offset;            /* as yolo2_augment_params */
+    int src_w, src_h;
+    int crop_x, crop_y, crop_w, crop_h;
+    int view_w, view_h;
+    int origin_x, origin_y;
+    int x0, y0, x1, y1;
+    unsigned flip;
+} yolo2_compose_tile;
+int yolo2_compose_images(const unsigned char *src, const yolo2_compose_tile *tiles, const yolo2_augment_params *photo,
+                         const float *mix, double *ws, float *out, int B, int L, int T, int H, int W, float fill,
+                         int any_contrast, void *stream);
+
 /* transform_labels (utils/data/__init__.py:112-145) for a batch: objects_coord [total,4] = (xmin,ymin,xmax,ymax) in
  * [0,1], objects_class [total], image b owns objects first_object[b] .. first_object[b+1]-1 (processed in order: the
  * last object of a cell wins, class bits accumulate).  Outputs are the loss's label tensors, each [B, cells, ...],

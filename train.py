@@ -14,6 +14,7 @@ objects_class [total], objects_coord [total,4] pixels, objects_first [N+1]); the
 input pipeline (utils/augment.py: crop / resize / colour augmentation per config.ini [data_augmentation_*], labels
 built on the GPU) -- the counterpart of the reference's load_image_labels after JPEG decode.  ``--data cache`` reads the
 reference's own TFRecord cache (<cachedir>/<profile>.tfrecord for every ``-p`` profile, utils/tfrecord.py) into HBM.
+``--mosaic P`` / ``--mixup P`` (``[mi355x] mosaic``, ``mixup``) compose training images of several dataset images on the device (utils/augment.py).
 ``--multiscale SPEC`` / ``[mi355x] multiscale`` trains at a size drawn from a list every ``--multiscale_every`` steps (yolo_tf_amd/multiscale.py)."""
 import argparse
 import configparser
@@ -61,6 +62,8 @@ def make_args(argv=None):
     parser.add_argument('--multiscale', default=None, help="overrides [mi355x] multiscale: input sizes drawn during training, entries S, WxH or LO-HI (squares in "
                         "steps of the network's stride) separated by spaces or commas, e.g. '320-608'; '' turns it off")
     parser.add_argument('--multiscale_every', default=None, type=int, help='overrides [mi355x] multiscale_every: steps a drawn size holds (default 10)')
+    parser.add_argument('--mosaic', default=None, type=float, help='overrides [mi355x] mosaic: probability that a training image is a 2x2 mosaic of four dataset images (0: off)')
+    parser.add_argument('--mixup', default=None, type=float, help='overrides [mi355x] mixup: probability that a training image is blended with a second one, MixUp (0: off)')
     parser.add_argument('--ckpt_format', default='npz', choices=['npz', 'tf'], help="checkpoint container: 'npz' (every optimizer) or 'tf' (TensorFlow V2 bundle, as the reference's tf.train.Saver writes)")
     return parser.parse_args(argv)
 
@@ -131,8 +134,29 @@ def multiscale_setting(args, config):
     return setting
 
 
+def compose_setting(args, config):
+    """[mi355x] mosaic / mixup and their companions with the command line's overrides (written into ``config``, where the input pipeline reads
+    them): None when both are off (nothing about the run changes), otherwise the options of utils.augment.compose_options.  Raises ValueError for
+    an invalid key and for data without raw objects, before anything is built."""
+    from yolo_tf_amd.utils.augment import compose_options
+    for key in ('mosaic', 'mixup'):
+        if getattr(args, key) is not None:
+            if not config.has_section('mi355x'):
+                config.add_section('mi355x')
+            config.set('mi355x', key, repr(getattr(args, key)))
+    options = compose_options(config)
+    if not (options['mosaic'] > 0 or options['mixup'] > 0):
+        return None
+    if args.data == 'synthetic' or (args.data != 'cache' and 'objects_coord' not in np.load(args.data, allow_pickle=True).files):
+        raise ValueError('[mi355x] mosaic = %g, mixup = %g: --data %s holds no raw objects; mosaic and MixUp compose training images from decoded '
+                         'images and their boxes (objects_class, objects_coord, objects_first in a .npz, or the dataset cache)'
+                         % (options['mosaic'], options['mixup'], args.data))
+    return options
+
+
 def main():
     setting = multiscale_setting(args, config)       # (a refusal comes before the process group and the device are touched)
+    composing = compose_setting(args, config)
     rank, local_rank, world = init_distributed()
     torch.cuda.set_device(local_rank)
     model = config.get('config', 'model')
@@ -161,6 +185,9 @@ def main():
         if added:
             logging.warning('multiscale: the configured size %dx%d was not in the list and is added' % (width, height))
         logging.warning('multiscale: sizes %s, a new draw every %d steps' % (multiscale.describe(sizes), every))
+    if composing is not None:
+        logging.warning('mosaic: probability %g, scale %g-%g, fill %g; mixup: probability %g, alpha %g' % (
+            composing['mosaic'], composing['mosaic_scale'][0], composing['mosaic_scale'][1], composing['mosaic_fill'], composing['mixup'], composing['mixup_alpha']))
     session = TrainSession(builder, args.batch_size, dtype=dtype, optimizer=args.optimizer, learning_rate=args.learning_rate,
                            gradient_clip=args.gradient_clip, config=config, seed=seed, world_size=world, sizes=sizes,
                            bucket_mb=config.getfloat('mi355x', 'bucket_mb') if config.has_option('mi355x', 'bucket_mb') else 64.0,

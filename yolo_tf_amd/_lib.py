@@ -56,6 +56,7 @@ SIGNATURES = {
     'yolo2_bn_leaky_pool_bwd_reduce': [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p],
     'yolo2_bn_leaky_pool_bwd_apply': [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p],
     'yolo2_augment_images': [_p, _p, _p, _p, _i, _i, _i, _i, _p],
+    'yolo2_compose_images': [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p],
     'yolo2_transform_labels': [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p],
     'yolo2_bn_stats': [_p, _p, _p, _p, _l, _i, _i, _p],
     'yolo2_bn_stats_ema': [_p, _p, _p, _p, _p, ctypes.c_double, _p, _l, _i, _i, _p],
@@ -183,6 +184,13 @@ class AugmentParams(ctypes.Structure):
     _fields_ = [('src_offset', ctypes.c_longlong), ('src_w', _i), ('src_h', _i), ('crop_x', _i), ('crop_y', _i), ('crop_w', _i), ('crop_h', _i),
                 ('flags', ctypes.c_uint), ('brightness', _f), ('saturation', _f), ('hue', _f), ('contrast', _f), ('noise_scale', _f),
                 ('noise_seed', ctypes.c_ulonglong)]
+
+
+class ComposeTile(ctypes.Structure):
+    """yolo2_compose_tile (include/yolo2_hip.h)."""
+    _fields_ = [('src_offset', ctypes.c_longlong), ('src_w', _i), ('src_h', _i), ('crop_x', _i), ('crop_y', _i), ('crop_w', _i), ('crop_h', _i),
+                ('view_w', _i), ('view_h', _i), ('origin_x', _i), ('origin_y', _i), ('x0', _i), ('y0', _i), ('x1', _i), ('y1', _i),
+                ('flip', ctypes.c_uint)]
 
 
 class HistJob(ctypes.Structure):

@@ -32,6 +32,7 @@ SOURCES = {
     'soft_nms.hip': ['-ffp-contract=off'],
     'tta.hip': ['-ffp-contract=off'],
     'augment.hip': ['-ffp-contract=off'],
+    'compose.hip': ['-ffp-contract=off'],
     'eval.hip': ['-ffp-contract=off'],
     'eval_coco.hip': ['-ffp-contract=off'],
     'anchors.hip': ['-ffp-contract=off'],

@@ -533,6 +533,11 @@ def augment_images(src, params_dev, ws, out, B, H, W, any_contrast):
     call('yolo2_augment_images', ptr(src), ptr(params_dev), ptr(ws), ptr(out), B, H, W, int(bool(any_contrast)), _stream())
 
 
+def compose_images(src, tiles_dev, photo_dev, mix_dev, ws, out, B, L, T, H, W, fill, any_contrast):
+    """Mosaic / MixUp: tiles_dev = the bytes of [B][L][T] ComposeTile, photo_dev of [B] AugmentParams, mix_dev of [B] f32 (None with L = 1)."""
+    call('yolo2_compose_images', ptr(src), ptr(tiles_dev), ptr(photo_dev), ptr(mix_dev), ptr(ws), ptr(out), B, L, T, H, W, float(fill), int(bool(any_contrast)), _stream())
+
+
 def transform_labels(objects_class, objects_coord, first_object, mask, prob, coords, offset_xy_min, offset_xy_max, areas, B, classes,
                      cell_width, cell_height, error_flag):
     call('yolo2_transform_labels', ptr(objects_class), ptr(objects_coord), ptr(first_object), ptr(mask), ptr(prob), ptr(coords),
