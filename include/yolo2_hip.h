@@ -392,6 +392,19 @@ int yolo2_loss_partials(const void *logits, int ld, const float *anchors, const 
                         const float *hparam, void *dlogits, float *ws, int B, int cell_h, int cell_w, int A, int C, int dtype,
                         void *stream);
 int yolo2_loss_objectives(const float *ws, float *objectives, int B, int cell_h, int cell_w, int A, void *stream);
+/* yolo2_loss / yolo2_loss_partials with the box regression loss chosen: box_loss 0 = mse (the two entries above, bit for bit), 1 = iou,
+ * 2 = giou, 3 = diou, 4 = ciou; anything else is an argument error.  In modes 1..4 the `coords` objective is sum(mask_best * (1 - q)) / cnt
+ * for the mode's score q of the predicted box against the cell's target (cell units relative to the cell) and
+ * channels 1..4 of dlogits hold its exact derivative, weighted by hparam[2]; every other output is what mode 0 writes.  Same workspace;
+ * yolo2_loss_objectives reduces the partials of every mode. */
+int yolo2_loss_box(const void *logits, int ld, const float *anchors, const float *mask,
+                   const float *prob, const float *coords, const float *off_min, const float *off_max,
+                   const float *areas, const float *hparam, float *objectives, void *dlogits,
+                   float *ws, int B, int cell_h, int cell_w, int A, int C, int dtype, void *stream, int box_loss);
+int yolo2_loss_box_partials(const void *logits, int ld, const float *anchors, const float *mask, const float *prob,
+                            const float *coords, const float *off_min, const float *off_max, const float *areas,
+                            const float *hparam, void *dlogits, float *ws, int B, int cell_h, int cell_w, int A, int C, int dtype,
+                            void *stream, int box_loss);
 
 /* ---- YOLO (v1) family, SURVEY 8f-4: model/yolo/__init__.py:37-100, model/yolo/inference.py:24-66 --------------------------
  * Network output row per image [cells*C class scores | cells*boxes*(iou, x, y, sqrt_w, sqrt_h)], all linear; `ld` = row stride.

@@ -15,7 +15,8 @@ input pipeline (utils/augment.py: crop / resize / colour augmentation per config
 built on the GPU) -- the counterpart of the reference's load_image_labels after JPEG decode.  ``--data cache`` reads the
 reference's own TFRecord cache (<cachedir>/<profile>.tfrecord for every ``-p`` profile, utils/tfrecord.py) into HBM.
 ``--mosaic P`` / ``--mixup P`` (``[mi355x] mosaic``, ``mixup``) compose training images of several dataset images on the device (utils/augment.py).
-``--multiscale SPEC`` / ``[mi355x] multiscale`` trains at a size drawn from a list every ``--multiscale_every`` steps (yolo_tf_amd/multiscale.py)."""
+``--multiscale SPEC`` / ``[mi355x] multiscale`` trains at a size drawn from a list every ``--multiscale_every`` steps (yolo_tf_amd/multiscale.py).
+``--box_loss MODE`` / ``[mi355x] box_loss`` regresses the responsible anchor's box with 1 - IoU / GIoU / DIoU / CIoU instead of the squared error (YOLOv2 family)."""
 import argparse
 import configparser
 import logging
@@ -30,7 +31,7 @@ import torch
 from yolo_tf_amd import checkpoint, multiscale, tf_checkpoint, utils
 from yolo_tf_amd.utils import events
 from yolo_tf_amd.parallel import agree, init_distributed, sync_replicas
-from yolo_tf_amd.session import TrainSession
+from yolo_tf_amd.session import BOX_LOSSES, TrainSession, box_loss_option
 from yolo_tf_amd.summary import HistogramSummaries, ImageSummaries
 from yolo_tf_amd.utils import data as udata
 
@@ -64,6 +65,8 @@ def make_args(argv=None):
     parser.add_argument('--multiscale_every', default=None, type=int, help='overrides [mi355x] multiscale_every: steps a drawn size holds (default 10)')
     parser.add_argument('--mosaic', default=None, type=float, help='overrides [mi355x] mosaic: probability that a training image is a 2x2 mosaic of four dataset images (0: off)')
     parser.add_argument('--mixup', default=None, type=float, help='overrides [mi355x] mixup: probability that a training image is blended with a second one, MixUp (0: off)')
+    parser.add_argument('--box_loss', default=None, choices=list(BOX_LOSSES), help='overrides [mi355x] box_loss: the box regression term of the YOLOv2 loss, mse (the '
+                        "reference's squared error; the default) or 1 - IoU / GIoU / DIoU / CIoU of the responsible anchor's box")
     parser.add_argument('--ckpt_format', default='npz', choices=['npz', 'tf'], help="checkpoint container: 'npz' (every optimizer) or 'tf' (TensorFlow V2 bundle, as the reference's tf.train.Saver writes)")
     return parser.parse_args(argv)
 
@@ -154,9 +157,20 @@ def compose_setting(args, config):
     return options
 
 
+def box_loss_setting(args, config):
+    """[mi355x] box_loss with the command line's override: one of session.BOX_LOSSES.  Raises ValueError for an unknown value and for the YOLO
+    (v1) family with anything but mse, before anything is built."""
+    box_loss = box_loss_option(args.box_loss, config)
+    if box_loss != 'mse' and config.get('config', 'model') == 'yolo':
+        raise ValueError('[mi355x] box_loss = %s: the IoU-family box losses cover the YOLOv2 family; the YOLO (v1) loss regresses its boxes with the '
+                         'squared error only' % box_loss)
+    return box_loss
+
+
 def main():
     setting = multiscale_setting(args, config)       # (a refusal comes before the process group and the device are touched)
     composing = compose_setting(args, config)
+    box_loss = box_loss_setting(args, config)
     rank, local_rank, world = init_distributed()
     torch.cuda.set_device(local_rank)
     model = config.get('config', 'model')
@@ -194,7 +208,11 @@ def main():
                            grad_dtype=config.get('mi355x', 'grad_dtype') if config.has_option('mi355x', 'grad_dtype') else 'f32',
                            sync_bn=config.getboolean('mi355x', 'sync_bn') if config.has_option('mi355x', 'sync_bn') else False,
                            shard_optimizer=config.getboolean('mi355x', 'shard_optimizer') if config.has_option('mi355x', 'shard_optimizer') else False,
-                           deterministic=True if args.deterministic else None)      # (None: [mi355x] deterministic / YOLO2_DETERMINISTIC decide)
+                           deterministic=True if args.deterministic else None,      # (None: [mi355x] deterministic / YOLO2_DETERMINISTIC decide)
+                           box_loss=box_loss)       # (always given: --box_loss mse must win over a config key; 'mse' is the call made before the option existed)
+    if session.box_loss != 'mse':
+        logging.warning('box_loss: %s (1 - %s of the responsible box, weighted by [yolo2_hparam] coords = %g)' % (
+            session.box_loss, {'iou': 'IoU', 'giou': 'GIoU', 'diou': 'DIoU', 'ciou': 'CIoU'}[session.box_loss], builder.hparam['coords']))
     logging.warning('optimizer=%s, dtype=%s, world=%d, parameters=%d%s' % (args.optimizer, dtype, world, session.engine.n_params,
                                                                           ', ema_decay=%g' % session.ema_decay if session.ema is not None else ''))
     # rank 0 alone chooses and reads the checkpoint; the others receive parameters, statistics, optimizer slots and

@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get('YOLO2_LIB_PATH') or os.path.join(_HERE, 'csrc', 'liby
 F32, BF16 = 0, 1
 I8_OUT_I8, I8_OUT_BF16, I8_OUT_F32, I8_OUT_ACC = 0, 1, 2, 3      # out_kind of yolo2_conv2d_i8
 NMS_METHODS = {'hard': 0, 'linear': 1, 'gaussian': 2}               # YOLO2_NMS_*: method of yolo2_soft_nms
+BOX_LOSSES = {'mse': 0, 'iou': 1, 'giou': 2, 'diou': 3, 'ciou': 4}   # box_loss of yolo2_loss_box / yolo2_loss_box_partials
 
 
 class HipKernelError(RuntimeError):
@@ -78,6 +79,8 @@ SIGNATURES = {
     'yolo2_loss': [_p, _i, _p, _p, _p, _p, _p, _p, _p, ctypes.POINTER(_f), _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
     'yolo2_loss_partials': [_p, _i, _p, _p, _p, _p, _p, _p, _p, ctypes.POINTER(_f), _p, _p, _i, _i, _i, _i, _i, _i, _p],
     'yolo2_loss_objectives': [_p, _p, _i, _i, _i, _i, _p],
+    'yolo2_loss_box': [_p, _i, _p, _p, _p, _p, _p, _p, _p, ctypes.POINTER(_f), _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _i],
+    'yolo2_loss_box_partials': [_p, _i, _p, _p, _p, _p, _p, _p, _p, ctypes.POINTER(_f), _p, _p, _i, _i, _i, _i, _i, _i, _p, _i],
     'yolo1_loss': [_p, _i, _p, _p, _p, _p, _p, _p, ctypes.POINTER(_f), _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
     'yolo1_head_decode': [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
     'yolo2_leaky_bwd': [_p, _p, _p, _l, _f, _i, _p],

@@ -9,10 +9,14 @@
 // The four objective sums are reduced wave -> block -> a deterministic second pass.
 #include "common.h"
 #pragma clang fp contract(off)
+#include "box_loss.h"
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
-template <typename T>
+// MODE (box_loss.h): Y2_BOX_MSE regresses the responsible anchor's box with the reference's squared error on (sx, sy, sqrt w, sqrt h); the
+// other modes put 1 - q of an IoU-family score in the `coords` slot and its closed-form gradient in channels 1..4, on the responsible lanes
+// only.  A compile-time parameter: the mse instantiation carries none of the new arithmetic, atan2f exists only in the CIoU one.
+template <typename T, int MODE>
 __global__ __launch_bounds__(256) void loss_kernel(
     const T *__restrict__ logits, int ld, const float *__restrict__ anchors, const float *__restrict__ mask,
     const float *__restrict__ prob, const float *__restrict__ coords, const float *__restrict__ off_min,
@@ -29,7 +33,7 @@ __global__ __launch_bounds__(256) void loss_kernel(
 
     float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;  // iou_best, iou_normal, coords, prob partial sums
     float iou = -INFINITY;
-    float z[5], sg[3], wh[2], sq[2], tc[4], m = 0.f;
+    float z[5], sg[3], wh[2], sq[2], tc[4], m = 0.f;      // (sq, tc -- sqrt of the predicted size in grid units, the `coords` label -- are the mse mode's alone)
     const T *lp = nullptr;
     if (act) {
         lp = logits + cell_id * ld + a * D;
@@ -42,8 +46,10 @@ __global__ __launch_bounds__(256) void loss_kernel(
         const float area_p = wh[0] * wh[1];
         const float hx = wh[0] / 2.0f, hy = wh[1] / 2.0f;
         const float pminx = sg[1] - hx, pminy = sg[2] - hy, pmaxx = sg[1] + hx, pmaxy = sg[2] + hy;
-        sq[0] = sqrtf(wh[0] / (float)cell_w);
-        sq[1] = sqrtf(wh[1] / (float)cell_h);
+        if constexpr (MODE == Y2_BOX_MSE) {
+            sq[0] = sqrtf(wh[0] / (float)cell_w);
+            sq[1] = sqrtf(wh[1] / (float)cell_h);
+        }
         m = mask[cell_id];
         const float tminx = off_min[cell_id * 2], tminy = off_min[cell_id * 2 + 1];
         const float tmaxx = off_max[cell_id * 2], tmaxy = off_max[cell_id * 2 + 1];
@@ -52,8 +58,10 @@ __global__ __launch_bounds__(256) void loss_kernel(
         const float inter = ix * iy;
         const float uni = fmaxf((areas[cell_id] + area_p) - inter, 1e-10f);
         iou = inter / uni;
+        if constexpr (MODE == Y2_BOX_MSE) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) tc[k] = coords[cell_id * 4 + k];
+            for (int k = 0; k < 4; ++k) tc[k] = coords[cell_id * 4 + k];
+        }
     }
     // best anchor of the cell: butterfly max inside the LPC-lane group
     float best = iou;
@@ -65,8 +73,16 @@ __global__ __launch_bounds__(256) void loss_kernel(
         const float iou_dist = d_iou * d_iou;
         s0 = mb * iou_dist;
         s1 = (1.0f - mb) * iou_dist;
-        const float dc0 = sg[1] - tc[0], dc1 = sg[2] - tc[1], dc2 = sq[0] - tc[2], dc3 = sq[1] - tc[3];
-        s2 = mb * (dc0 * dc0) + mb * (dc1 * dc1) + mb * (dc2 * dc2) + mb * (dc3 * dc3);
+        float dc0 = 0.f, dc1 = 0.f, dc2 = 0.f, dc3 = 0.f;      // mse: prediction - label of (sx, sy, sqrt w, sqrt h)
+        float gbox[4] = {0.f, 0.f, 0.f, 0.f};                  // the other modes: dq / d(sx, sy, w, h) of a responsible lane
+        if constexpr (MODE == Y2_BOX_MSE) {
+            dc0 = sg[1] - tc[0], dc1 = sg[2] - tc[1], dc2 = sq[0] - tc[2], dc3 = sq[1] - tc[3];
+            s2 = mb * (dc0 * dc0) + mb * (dc1 * dc1) + mb * (dc2 * dc2) + mb * (dc3 * dc3);
+        } else if (mb != 0.0f) {
+            const float q = box_score<MODE>(sg[1], sg[2], wh[0], wh[1], off_min[cell_id * 2], off_min[cell_id * 2 + 1], off_max[cell_id * 2],
+                                            off_max[cell_id * 2 + 1], areas[cell_id], gbox);
+            s2 = mb * (1.0f - q);
+        }
         // softmax over classes (two passes over the logits; they are L1-resident).  Only the responsible anchors need it: the class term
         // and its gradient carry the factor mask_best (model/yolo2/__init__.py:87,94), which is 0 for every other lane -- a handful of
         // lanes per image instead of all 845 (with 80 classes the three class loops were 2/3 of this kernel: 45 -> 15 us at batch 8).
@@ -91,10 +107,21 @@ __global__ __launch_bounds__(256) void loss_kernel(
             T *dp = dlogits + cell_id * ld + a * D;
             const float w_obj = w_best * mb + w_normal * (1.0f - mb);
             dp[0] = (T)(2.0f * (sg[0] - mb) * w_obj / cnt * sg[0] * (1.0f - sg[0]));
-            dp[1] = (T)(2.0f * mb * dc0 * w_coords / cnt * sg[1] * (1.0f - sg[1]));
-            dp[2] = (T)(2.0f * mb * dc1 * w_coords / cnt * sg[2] * (1.0f - sg[2]));
-            dp[3] = (T)(2.0f * mb * dc2 * w_coords / cnt * sq[0] / 2.0f);
-            dp[4] = (T)(2.0f * mb * dc3 * w_coords / cnt * sq[1] / 2.0f);
+            if constexpr (MODE == Y2_BOX_MSE) {
+                dp[1] = (T)(2.0f * mb * dc0 * w_coords / cnt * sg[1] * (1.0f - sg[1]));
+                dp[2] = (T)(2.0f * mb * dc1 * w_coords / cnt * sg[2] * (1.0f - sg[2]));
+                dp[3] = (T)(2.0f * mb * dc2 * w_coords / cnt * sq[0] / 2.0f);
+                dp[4] = (T)(2.0f * mb * dc3 * w_coords / cnt * sq[1] / 2.0f);
+            } else if (resp) {
+                // d(w_coords * mb * (1 - q) / cnt) through sx = sigmoid(z1), sy = sigmoid(z2), w = exp(z3) * aw, h = exp(z4) * ah
+                const float gc = -(mb * w_coords / cnt);
+                dp[1] = (T)(gc * gbox[0] * dsigmoidf_(z[1]));
+                dp[2] = (T)(gc * gbox[1] * dsigmoidf_(z[2]));
+                dp[3] = (T)(gc * gbox[2] * wh[0]);
+                dp[4] = (T)(gc * gbox[3] * wh[1]);
+            } else {
+                for (int k = 1; k < 5; ++k) dp[k] = (T)0.f;
+            }
             if (resp) {
                 for (int k = 0; k < C; ++k) {
                     float p = expf((float)lp[5 + k] - mx) / den;
@@ -138,8 +165,9 @@ static int lanes_per_cell(int A) {
 static int loss_impl(const void *logits, int ld, const float *anchors, const float *mask, const float *prob,
                      const float *coords, const float *off_min, const float *off_max, const float *areas,
                      const float *hparam, float *objectives, void *dlogits, float *ws, int B, int cell_h,
-                     int cell_w, int A, int C, int dtype, void *stream) {
+                     int cell_w, int A, int C, int dtype, void *stream, int box_loss = Y2_BOX_MSE) {
     Y2_CHECK_ARG(logits && anchors && mask && prob && coords && off_min && off_max && areas && hparam && ws);
+    Y2_CHECK_ARG(box_loss >= 0 && box_loss < Y2_BOX_MODES);
     Y2_CHECK_ARG(B > 0 && cell_h > 0 && cell_w > 0 && A > 0 && A <= 64 && C > 0 && ld >= A * (5 + C));
     hipStream_t st = (hipStream_t)stream;
     const int LPC = lanes_per_cell(A);
@@ -148,8 +176,18 @@ static int loss_impl(const void *logits, int ld, const float *anchors, const flo
     float hp[4];
     // hparam is a host pointer: 4 weights {iou_best, iou_normal, coords, prob}
     hp[0] = hparam[0]; hp[1] = hparam[1]; hp[2] = hparam[2]; hp[3] = hparam[3];
-    Y2_DISPATCH_DTYPE(dtype, loss_kernel<T><<<nblocks, 256, 0, st>>>((const T *)logits, ld, anchors, mask, prob, coords, off_min, off_max, areas,
-                                                                     hp[0], hp[1], hp[2], hp[3], (T *)dlogits, ws, B, cell_h, cell_w, A, C, LPC));
+#define Y2_LOSS_LAUNCH(MODE)                                                                                                                     \
+    Y2_DISPATCH_DTYPE(dtype, (loss_kernel<T, MODE><<<nblocks, 256, 0, st>>>((const T *)logits, ld, anchors, mask, prob, coords, off_min, off_max, \
+                                                                            areas, hp[0], hp[1], hp[2], hp[3], (T *)dlogits, ws, B, cell_h,     \
+                                                                            cell_w, A, C, LPC)))
+    switch (box_loss) {
+        case Y2_BOX_MSE: Y2_LOSS_LAUNCH(Y2_BOX_MSE); break;
+        case Y2_BOX_IOU: Y2_LOSS_LAUNCH(Y2_BOX_IOU); break;
+        case Y2_BOX_GIOU: Y2_LOSS_LAUNCH(Y2_BOX_GIOU); break;
+        case Y2_BOX_DIOU: Y2_LOSS_LAUNCH(Y2_BOX_DIOU); break;
+        default: Y2_LOSS_LAUNCH(Y2_BOX_CIOU); break;
+    }
+#undef Y2_LOSS_LAUNCH
     if (objectives) loss_finalize_kernel<<<1, 256, 0, st>>>(ws, nblocks, (float)((long)B * cell_h * cell_w * A), objectives);
     Y2_CHECK_LAUNCH();
     return YOLO2_OK;
@@ -174,6 +212,21 @@ extern "C" int yolo2_loss_partials(const void *logits, int ld, const float *anch
                                    const float *coords, const float *off_min, const float *off_max, const float *areas,
                                    const float *hparam, void *dlogits, float *ws, int B, int cell_h, int cell_w, int A, int C, int dtype, void *stream) {
     return loss_impl(logits, ld, anchors, mask, prob, coords, off_min, off_max, areas, hparam, nullptr, dlogits, ws, B, cell_h, cell_w, A, C, dtype, stream);
+}
+// The same two entries with the box regression loss chosen (box_loss.h: 0 = mse, today's loss, bit for bit; 1 = iou, 2 = giou, 3 = diou, 4 = ciou).
+// Workspace and yolo2_loss_objectives serve every mode.
+extern "C" int yolo2_loss_box(const void *logits, int ld, const float *anchors, const float *mask, const float *prob,
+                              const float *coords, const float *off_min, const float *off_max, const float *areas,
+                              const float *hparam, float *objectives, void *dlogits, float *ws, int B, int cell_h,
+                              int cell_w, int A, int C, int dtype, void *stream, int box_loss) {
+    Y2_CHECK_ARG(objectives);
+    return loss_impl(logits, ld, anchors, mask, prob, coords, off_min, off_max, areas, hparam, objectives, dlogits, ws, B, cell_h, cell_w, A, C, dtype, stream, box_loss);
+}
+extern "C" int yolo2_loss_box_partials(const void *logits, int ld, const float *anchors, const float *mask, const float *prob,
+                                       const float *coords, const float *off_min, const float *off_max, const float *areas,
+                                       const float *hparam, void *dlogits, float *ws, int B, int cell_h, int cell_w, int A, int C, int dtype,
+                                       void *stream, int box_loss) {
+    return loss_impl(logits, ld, anchors, mask, prob, coords, off_min, off_max, areas, hparam, nullptr, dlogits, ws, B, cell_h, cell_w, A, C, dtype, stream, box_loss);
 }
 extern "C" int yolo2_loss_objectives(const float *ws, float *objectives, int B, int cell_h, int cell_w, int A, void *stream) {
     Y2_CHECK_ARG(ws && objectives && B > 0 && cell_h > 0 && cell_w > 0 && A > 0 && A <= 64);

@@ -305,21 +305,40 @@ def head_decode_attrs(logits, ld, anchors, iou, prob, xy, wh, B, ch, cw, A, C):
          dtype_code(logits.dtype), _stream())
 
 
-def loss(logits, ld, anchors, labels, hparam, objectives, dlogits, ws, B, ch, cw, A, C):
+def box_loss_code(box_loss):
+    """'mse' | 'iou' | 'giou' | 'diou' | 'ciou' -> the int of yolo2_loss_box; anything else raises ValueError (host only)."""
+    try:
+        return _lib.BOX_LOSSES[box_loss]
+    except (KeyError, TypeError):
+        raise ValueError('box_loss = %r: one of %s' % (box_loss, ', '.join(_lib.BOX_LOSSES)))
+
+
+def loss(logits, ld, anchors, labels, hparam, objectives, dlogits, ws, B, ch, cw, A, C, box_loss='mse'):
     """labels: 6 device f32 tensors (mask, prob, coords, off_min, off_max, areas); hparam: 4 host floats
-    in the order iou_best, iou_normal, coords, prob."""
+    in the order iou_best, iou_normal, coords, prob.  ``box_loss``: 'mse' (the reference's squared error, the call made before the option
+    existed) or 'iou' / 'giou' / 'diou' / 'ciou' (DESIGN.md section 21)."""
+    mode = box_loss_code(box_loss)
     hp = (ctypes.c_float * 4)(*[float(v) for v in hparam])
     mask, prob, coords, omin, omax, areas = labels
-    call('yolo2_loss', ptr(logits), ld, ptr(anchors), ptr(mask), ptr(prob), ptr(coords), ptr(omin), ptr(omax), ptr(areas), hp,
-         ptr(objectives), ptr(dlogits), ptr(ws), B, ch, cw, A, C, dtype_code(logits.dtype), _stream())
+    if mode == 0:
+        call('yolo2_loss', ptr(logits), ld, ptr(anchors), ptr(mask), ptr(prob), ptr(coords), ptr(omin), ptr(omax), ptr(areas), hp,
+             ptr(objectives), ptr(dlogits), ptr(ws), B, ch, cw, A, C, dtype_code(logits.dtype), _stream())
+    else:
+        call('yolo2_loss_box', ptr(logits), ld, ptr(anchors), ptr(mask), ptr(prob), ptr(coords), ptr(omin), ptr(omax), ptr(areas), hp,
+             ptr(objectives), ptr(dlogits), ptr(ws), B, ch, cw, A, C, dtype_code(logits.dtype), _stream(), mode)
 
 
-def loss_partials(logits, ld, anchors, labels, hparam, dlogits, ws, B, ch, cw, A, C):
-    """The loss kernel alone: dlogits + per-workgroup partial sums in ``ws``; ``loss_objectives`` reduces them on demand."""
+def loss_partials(logits, ld, anchors, labels, hparam, dlogits, ws, B, ch, cw, A, C, box_loss='mse'):
+    """The loss kernel alone: dlogits + per-workgroup partial sums in ``ws``; ``loss_objectives`` reduces them on demand.  ``box_loss`` as in ``loss``."""
+    mode = box_loss_code(box_loss)
     hp = (ctypes.c_float * 4)(*[float(v) for v in hparam])
     mask, prob, coords, omin, omax, areas = labels
-    call('yolo2_loss_partials', ptr(logits), ld, ptr(anchors), ptr(mask), ptr(prob), ptr(coords), ptr(omin), ptr(omax), ptr(areas), hp,
-         ptr(dlogits), ptr(ws), B, ch, cw, A, C, dtype_code(logits.dtype), _stream())
+    if mode == 0:
+        call('yolo2_loss_partials', ptr(logits), ld, ptr(anchors), ptr(mask), ptr(prob), ptr(coords), ptr(omin), ptr(omax), ptr(areas), hp,
+             ptr(dlogits), ptr(ws), B, ch, cw, A, C, dtype_code(logits.dtype), _stream())
+    else:
+        call('yolo2_loss_box_partials', ptr(logits), ld, ptr(anchors), ptr(mask), ptr(prob), ptr(coords), ptr(omin), ptr(omax), ptr(areas), hp,
+             ptr(dlogits), ptr(ws), B, ch, cw, A, C, dtype_code(logits.dtype), _stream(), mode)
 
 
 def loss_objectives(ws, objectives, B, ch, cw, A):

@@ -29,6 +29,20 @@ def ema_decay_option(ema_decay, config):
     return decay
 
 
+BOX_LOSSES = ('mse', 'iou', 'giou', 'diou', 'ciou')
+
+
+def box_loss_option(box_loss, config):
+    """The ``box_loss`` of a TrainSession: the argument, or ``[mi355x] box_loss`` of the config when the argument is None; absent = 'mse'.
+    Anything but mse, iou, giou, diou, ciou raises ValueError.  Pure host logic."""
+    if box_loss is None:
+        box_loss = config.get('mi355x', 'box_loss') if config is not None and config.has_option('mi355x', 'box_loss') else 'mse'
+    name = str(box_loss).strip().lower()
+    if name not in BOX_LOSSES:
+        raise ValueError('box_loss = %r: the box regression loss is one of %s (absent: mse)' % (box_loss, ', '.join(BOX_LOSSES)))
+    return name
+
+
 def ema_decay_at(ema_decay, t):
     """[TF-sem] tf.train.ExponentialMovingAverage(decay, num_updates=t): min(decay, (1 + t) / (10 + t)), in Python floats."""
     return min(ema_decay, (1.0 + t) / (10.0 + t))
@@ -41,7 +55,7 @@ class TrainSession(object):
 
     def __init__(self, builder, batch_size, dtype='bf16', optimizer='adam', learning_rate=1e-6, gradient_clip=0.0,
                  config=None, seed=0, world_size=1, bucket_mb=64.0, preprocess_mode=0, sizes=None, grad_dtype='f32', comm_cus=None, comm_timing=False,
-                 sync_bn=False, shard_optimizer=False, deterministic=None, ema_decay=None):
+                 sync_bn=False, shard_optimizer=False, deterministic=None, ema_decay=None, box_loss=None):
         """``sizes``: optional list of (width, height) input sizes for multi-scale training (BASELINE configs[3]); buffers are
         allocated once for the largest, ``set_size`` switches between them, the builder's configured size is selected first.
 
@@ -51,14 +65,20 @@ class TrainSession(object):
         family only; with world_size > 1 the local computation is deterministic but nothing is promised across the collective.
 
         ``ema_decay``: exponential moving average of the trainable arena (weight averaging), updated once per step after the optimizer.
-        None (default): ``[mi355x] ema_decay`` of the config; absent or 0: off -- ``session.ema`` is None, nothing is allocated or launched."""
+        None (default): ``[mi355x] ema_decay`` of the config; absent or 0: off -- ``session.ema`` is None, nothing is allocated or launched.
+
+        ``box_loss``: the box regression term of the YOLOv2 loss: 'mse' (the reference's squared error) or 'iou', 'giou',
+        'diou', 'ciou'.  None (default): ``[mi355x] box_loss`` of the config; absent or 'mse': the loss call made before the option existed."""
         assert builder.training, 'call builder(data, training=True) first'
         self.ema_decay = ema_decay_option(ema_decay, config if config is not None else getattr(builder, 'config', None))
+        self.box_loss = box_loss_option(box_loss, config if config is not None else getattr(builder, 'config', None))
         self.builder = builder
         self.B = batch_size
         own = (builder.width, builder.height)
         traced = {own: (builder.graph, builder.model)}
         self.v1 = getattr(builder, 'family', 'yolo2') == 'yolo'       # YOLO (v1): linear fully connected head, boxes_per_cell instead of anchors
+        if self.v1 and self.box_loss != 'mse':
+            raise NotImplementedError('box_loss = %s covers the YOLOv2 family: the YOLO (v1) loss regresses its boxes with the squared error only' % self.box_loss)
         assert not (self.v1 and sizes), 'the fully connected YOLO (v1) head fixes the input size'
         for wh in (sizes or []):
             wh = (int(wh[0]), int(wh[1]))
@@ -181,7 +201,9 @@ class TrainSession(object):
             ops.yolo1_loss(logits, ld, self.labels, self.hparam, self.objectives_dev, dlogits, self.loss_ws, self.B, m.cell_height, m.cell_width, self.A, self.C)
         else:
             # (the four objective values are reduced from the partial sums when fetch() asks for them)
-            ops.loss_partials(logits, ld, self.anchors, self.labels, self.hparam, dlogits, self.loss_ws, self.B, m.cell_height, m.cell_width, self.A, self.C)
+            # (box_loss 'mse' is yolo2_loss_partials, the call made before the option existed; the other modes take yolo2_loss_box_partials)
+            ops.loss_partials(logits, ld, self.anchors, self.labels, self.hparam, dlogits, self.loss_ws, self.B, m.cell_height, m.cell_width, self.A, self.C,
+                              box_loss=self.box_loss)
             self._objectives_pending = (m.cell_height, m.cell_width)
         if self.reducer is not None:
             self.reducer.begin()
