@@ -405,6 +405,33 @@ int yolo2_loss_box_partials(const void *logits, int ld, const float *anchors, co
                             const float *coords, const float *off_min, const float *off_max, const float *areas,
                             const float *hparam, void *dlogits, float *ws, int B, int cell_h, int cell_w, int A, int C, int dtype,
                             void *stream, int box_loss);
+/* Every option of the YOLOv2 loss in one struct; later options join it.  With {sizeof, 0, 0, 0, 0, 0, any} the two
+ * entries below are yolo2_loss / yolo2_loss_partials, with only box_loss set yolo2_loss_box / yolo2_loss_box_partials, bit for bit.
+ *   ignore_thresh t: a lane that is not responsible and whose predicted box has an IoU above t (strictly) with a ground truth box of its
+ *     image -- the object cells of the label tensors, one box per cell: cell_xy + off_min .. cell_xy + off_max, area `areas` -- takes no part
+ *     in iou_normal and gets no objectness gradient.  cnt is not renormalised.
+ *   rescore: the objectness target of a responsible lane is its own matching IoU (a constant in the derivative) instead of 1.
+ *   class_loss: 0 the squared error on the softmax; 1 the cross-entropy -sum_k tt_k log p_k; 2 focal, -sum_k tt_k (1 - p_k)^gamma log p_k, on
+ *     tt_k = (1 - eps) t_k + eps * sum(t) / C of the (possibly multi-hot) label row t; in the `prob` objective and the class channels of dlogits.
+ * A NULL opt, a size other than sizeof(yolo2_loss_options), an out-of-range or non-finite field, and label_smoothing != 0 with class_loss 0
+ * are argument errors: nothing is launched, nothing is written.  Same workspace; yolo2_loss_objectives reduces the partials of every mode. */
+typedef struct yolo2_loss_options {
+    int   size;             /* sizeof(yolo2_loss_options): a larger, later struct is refused by an older library and vice versa */
+    int   box_loss;         /* as yolo2_loss_box */
+    int   class_loss;       /* 0 mse, 1 ce, 2 focal */
+    int   rescore;          /* 0 | 1 */
+    float ignore_thresh;    /* 0 = off, else 0 < t < 1 */
+    float label_smoothing;  /* 0 <= eps < 1; must be 0 with class_loss mse */
+    float focal_gamma;      /* 0 or >= 1; read with class_loss focal only */
+} yolo2_loss_options;
+int yolo2_loss_ex(const void *logits, int ld, const float *anchors, const float *mask,
+                  const float *prob, const float *coords, const float *off_min, const float *off_max,
+                  const float *areas, const float *hparam, float *objectives, void *dlogits,
+                  float *ws, int B, int cell_h, int cell_w, int A, int C, int dtype, void *stream, const yolo2_loss_options *opt);
+int yolo2_loss_ex_partials(const void *logits, int ld, const float *anchors, const float *mask, const float *prob,
+                           const float *coords, const float *off_min, const float *off_max, const float *areas,
+                           const float *hparam, void *dlogits, float *ws, int B, int cell_h, int cell_w, int A, int C, int dtype,
+                           void *stream, const yolo2_loss_options *opt);
 
 /* ---- YOLO (v1) family, SURVEY 8f-4: model/yolo/__init__.py:37-100, model/yolo/inference.py:24-66 --------------------------
  * Network output row per image [cells*C class scores | cells*boxes*(iou, x, y, sqrt_w, sqrt_h)], all linear; `ld` = row stride.

@@ -16,7 +16,9 @@ built on the GPU) -- the counterpart of the reference's load_image_labels after 
 reference's own TFRecord cache (<cachedir>/<profile>.tfrecord for every ``-p`` profile, utils/tfrecord.py) into HBM.
 ``--mosaic P`` / ``--mixup P`` (``[mi355x] mosaic``, ``mixup``) compose training images of several dataset images on the device (utils/augment.py).
 ``--multiscale SPEC`` / ``[mi355x] multiscale`` trains at a size drawn from a list every ``--multiscale_every`` steps (yolo_tf_amd/multiscale.py).
-``--box_loss MODE`` / ``[mi355x] box_loss`` regresses the responsible anchor's box with 1 - IoU / GIoU / DIoU / CIoU instead of the squared error (YOLOv2 family)."""
+``--box_loss MODE`` / ``[mi355x] box_loss`` regresses the responsible anchor's box with 1 - IoU / GIoU / DIoU / CIoU instead of the squared error (YOLOv2 family).
+``--ignore_thresh T``, ``--rescore``, ``--class_loss mse|ce|focal``, ``--label_smoothing E``, ``--focal_gamma G`` (and the ``[mi355x]`` keys of the same names) are the other
+options of the YOLOv2 loss: Darknet's ignore threshold, the IoU objectness target, a cross-entropy or focal class term."""
 import argparse
 import configparser
 import logging
@@ -31,7 +33,7 @@ import torch
 from yolo_tf_amd import checkpoint, multiscale, tf_checkpoint, utils
 from yolo_tf_amd.utils import events
 from yolo_tf_amd.parallel import agree, init_distributed, sync_replicas
-from yolo_tf_amd.session import BOX_LOSSES, TrainSession, box_loss_option
+from yolo_tf_amd.session import BOX_LOSSES, CLASS_LOSSES, TrainSession, box_loss_option, loss_options, loss_options_set
 from yolo_tf_amd.summary import HistogramSummaries, ImageSummaries
 from yolo_tf_amd.utils import data as udata
 
@@ -67,6 +69,14 @@ def make_args(argv=None):
     parser.add_argument('--mixup', default=None, type=float, help='overrides [mi355x] mixup: probability that a training image is blended with a second one, MixUp (0: off)')
     parser.add_argument('--box_loss', default=None, choices=list(BOX_LOSSES), help='overrides [mi355x] box_loss: the box regression term of the YOLOv2 loss, mse (the '
                         "reference's squared error; the default) or 1 - IoU / GIoU / DIoU / CIoU of the responsible anchor's box")
+    parser.add_argument('--class_loss', default=None, choices=list(CLASS_LOSSES), help="overrides [mi355x] class_loss: the class term of the YOLOv2 loss, mse (the reference's "
+                        'squared error on the softmax; the default), ce (cross-entropy) or focal')
+    parser.add_argument('--ignore_thresh', default=None, type=float, help='overrides [mi355x] ignore_thresh: a lane that is not responsible and predicts a ground truth box '
+                        'with an IoU above this is left out of the no-object term (Darknet: 0.6; 0: off)')
+    parser.add_argument('--rescore', default=None, action='store_true', help="[mi355x] rescore: the responsible anchor's objectness target is its IoU instead of 1")
+    parser.add_argument('--no_rescore', dest='rescore', action='store_false', help='turns [mi355x] rescore off')
+    parser.add_argument('--label_smoothing', default=None, type=float, help='overrides [mi355x] label_smoothing: epsilon of the ce / focal class target (0: off)')
+    parser.add_argument('--focal_gamma', default=None, type=float, help='overrides [mi355x] focal_gamma: the focusing exponent of class_loss focal, 0 or >= 1 (default 2)')
     parser.add_argument('--ckpt_format', default='npz', choices=['npz', 'tf'], help="checkpoint container: 'npz' (every optimizer) or 'tf' (TensorFlow V2 bundle, as the reference's tf.train.Saver writes)")
     return parser.parse_args(argv)
 
@@ -167,10 +177,32 @@ def box_loss_setting(args, config):
     return box_loss
 
 
+def loss_setting(args, config):
+    """Every loss option ([mi355x] box_loss, class_loss, ignore_thresh, rescore, label_smoothing, focal_gamma) with the command line's overrides, as
+    session.loss_options returns them.  Raises ValueError for an invalid value and for the YOLO (v1) family with any option on, before anything is built."""
+    box_loss_setting(args, config)       # (called for its refusals only: unknown mode, YOLO (v1) with another mode than mse; loss_options resolves the value again)
+    options = loss_options(config, args.box_loss, args.class_loss, args.ignore_thresh, args.rescore, args.label_smoothing, args.focal_gamma)
+    on = loss_options_set(options)
+    if on and config.get('config', 'model') == 'yolo':
+        raise ValueError('[mi355x] %s = %s: the loss options cover the YOLOv2 family; the YOLO (v1) loss has its own objectness and class terms only' % (on[0], options[on[0]]))
+    return options
+
+
+def describe_loss_options(options):
+    """One line for the log: the options of DESIGN.md section 22 that are on, or None."""
+    on = loss_options_set(options)
+    if not on:
+        return None
+    parts = ['%s=%s' % (k, options[k]) for k in on]
+    if options['class_loss'] == 'focal':
+        parts.append('focal_gamma=%g' % options['focal_gamma'])
+    return 'loss options: ' + ', '.join(parts)
+
+
 def main():
     setting = multiscale_setting(args, config)       # (a refusal comes before the process group and the device are touched)
     composing = compose_setting(args, config)
-    box_loss = box_loss_setting(args, config)
+    options = loss_setting(args, config)
     rank, local_rank, world = init_distributed()
     torch.cuda.set_device(local_rank)
     model = config.get('config', 'model')
@@ -209,10 +241,12 @@ def main():
                            sync_bn=config.getboolean('mi355x', 'sync_bn') if config.has_option('mi355x', 'sync_bn') else False,
                            shard_optimizer=config.getboolean('mi355x', 'shard_optimizer') if config.has_option('mi355x', 'shard_optimizer') else False,
                            deterministic=True if args.deterministic else None,      # (None: [mi355x] deterministic / YOLO2_DETERMINISTIC decide)
-                           box_loss=box_loss)       # (always given: --box_loss mse must win over a config key; 'mse' is the call made before the option existed)
+                           **options)       # (always given: --box_loss mse must win over a config key; all off is the call made before the options existed)
     if session.box_loss != 'mse':
         logging.warning('box_loss: %s (1 - %s of the responsible box, weighted by [yolo2_hparam] coords = %g)' % (
             session.box_loss, {'iou': 'IoU', 'giou': 'GIoU', 'diou': 'DIoU', 'ciou': 'CIoU'}[session.box_loss], builder.hparam['coords']))
+    if describe_loss_options(session.loss_options):
+        logging.warning(describe_loss_options(session.loss_options))
     logging.warning('optimizer=%s, dtype=%s, world=%d, parameters=%d%s' % (args.optimizer, dtype, world, session.engine.n_params,
                                                                           ', ema_decay=%g' % session.ema_decay if session.ema is not None else ''))
     # rank 0 alone chooses and reads the checkpoint; the others receive parameters, statistics, optimizer slots and

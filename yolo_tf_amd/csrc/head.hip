@@ -10,19 +10,23 @@
 #include "common.h"
 #pragma clang fp contract(off)
 #include "box_loss.h"
+#include "loss_opts.h"
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // MODE (box_loss.h): Y2_BOX_MSE regresses the responsible anchor's box with the reference's squared error on (sx, sy, sqrt w, sqrt h); the
 // other modes put 1 - q of an IoU-family score in the `coords` slot and its closed-form gradient in channels 1..4, on the responsible lanes
 // only.  A compile-time parameter: the mse instantiation carries none of the new arithmetic, atan2f exists only in the CIoU one.
-template <typename T, int MODE>
+// CLS and EXT (loss_opts.h): the class term (Y2_CLS_MSE: the reference's squared error on the softmax) and whether the launch carries the ignore
+// threshold / the IoU objectness target, both read from `opt` behind workgroup-uniform branches.  <T, MODE, Y2_CLS_MSE, false> is the kernel as
+// it was before these options existed.
+template <typename T, int MODE, int CLS, bool EXT>
 __global__ __launch_bounds__(256) void loss_kernel(
     const T *__restrict__ logits, int ld, const float *__restrict__ anchors, const float *__restrict__ mask,
     const float *__restrict__ prob, const float *__restrict__ coords, const float *__restrict__ off_min,
     const float *__restrict__ off_max, const float *__restrict__ areas, float w_best, float w_normal,
     float w_coords, float w_prob, T *__restrict__ dlogits, float *__restrict__ partial, int B, int cell_h,
-    int cell_w, int A, int C, int LPC) {
+    int cell_w, int A, int C, int LPC, loss_opts opt) {
     const int cells = cell_h * cell_w;
     const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long cell_id = gid / LPC;  // flat (b, cell)
@@ -35,6 +39,7 @@ __global__ __launch_bounds__(256) void loss_kernel(
     float iou = -INFINITY;
     float z[5], sg[3], wh[2], sq[2], tc[4], m = 0.f;      // (sq, tc -- sqrt of the predicted size in grid units, the `coords` label -- are the mse mode's alone)
     const T *lp = nullptr;
+    float gx1 = 0.f, gy1 = 0.f, gx2 = 0.f, gy2 = 0.f, garea = 0.f;      // EXT: the predicted box in grid units (cell_xy + offset_xy_min / max) and its area
     if (act) {
         lp = logits + cell_id * ld + a * D;
 #pragma unroll
@@ -46,6 +51,11 @@ __global__ __launch_bounds__(256) void loss_kernel(
         const float area_p = wh[0] * wh[1];
         const float hx = wh[0] / 2.0f, hy = wh[1] / 2.0f;
         const float pminx = sg[1] - hx, pminy = sg[2] - hy, pmaxx = sg[1] + hx, pmaxy = sg[2] + hy;
+        if constexpr (EXT) {
+            const int cell = (int)(cell_id % cells);
+            const float cx = (float)(cell % cell_w), cy = (float)(cell / cell_w);
+            gx1 = cx + pminx, gy1 = cy + pminy, gx2 = cx + pmaxx, gy2 = cy + pmaxy, garea = area_p;
+        }
         if constexpr (MODE == Y2_BOX_MSE) {
             sq[0] = sqrtf(wh[0] / (float)cell_w);
             sq[1] = sqrtf(wh[1] / (float)cell_h);
@@ -66,13 +76,24 @@ __global__ __launch_bounds__(256) void loss_kernel(
     // best anchor of the cell: butterfly max inside the LPC-lane group
     float best = iou;
     for (int o = LPC >> 1; o > 0; o >>= 1) best = fmaxf(best, __shfl_xor(best, o, 64));
+    // ignore threshold: M = the largest IoU of the lane's box with a ground truth box of its image (every thread takes part in the staging)
+    float M = 0.f;
+    if constexpr (EXT) {
+        if (opt.ignore_thresh > 0.0f) M = gt_scan(mask, off_min, off_max, areas, B, cells, cell_w, LPC, act, cell_id, gx1, gy1, gx2, gy2, garea);
+    }
 
     if (act) {
         const float mb = m * (iou == best ? 1.0f : 0.0f);
-        const float d_iou = sg[0] - mb;
+        float tgt = mb;                  // the objectness target: 1 on the responsible lanes (their own matching IoU with rescore), 0 elsewhere
+        bool ignored = false;            // not responsible and M > ignore_thresh: no part in iou_normal, no objectness gradient
+        if constexpr (EXT) {
+            if (opt.rescore && mb != 0.0f) tgt = iou;
+            ignored = opt.ignore_thresh > 0.0f && mb == 0.0f && M > opt.ignore_thresh;
+        }
+        const float d_iou = sg[0] - tgt;
         const float iou_dist = d_iou * d_iou;
         s0 = mb * iou_dist;
-        s1 = (1.0f - mb) * iou_dist;
+        s1 = ignored ? 0.0f : (1.0f - mb) * iou_dist;
         float dc0 = 0.f, dc1 = 0.f, dc2 = 0.f, dc3 = 0.f;      // mse: prediction - label of (sx, sy, sqrt w, sqrt h)
         float gbox[4] = {0.f, 0.f, 0.f, 0.f};                  // the other modes: dq / d(sx, sy, w, h) of a responsible lane
         if constexpr (MODE == Y2_BOX_MSE) {
@@ -91,7 +112,12 @@ __global__ __launch_bounds__(256) void loss_kernel(
         const float *tp = prob + cell_id * C;
         float sp = 0.f, dot = 0.f;
         const float gp = 2.0f * mb * w_prob / cnt;
-        if (resp) {
+        if constexpr (CLS != Y2_CLS_MSE) {
+            // cross-entropy / focal (loss_opts.h): objective and gradient of a responsible lane in one call, the other lanes' class channels zeroed
+            T *dcls = dlogits ? dlogits + cell_id * ld + a * D + 5 : nullptr;
+            if (resp) sp = class_term<CLS == Y2_CLS_FOCAL, T>(lp + 5, tp, C, opt.label_smoothing, opt.focal_gamma, mb * w_prob / cnt, dcls);
+            else if (dcls) for (int k = 0; k < C; ++k) dcls[k] = (T)0.f;
+        } else if (resp) {
             for (int k = 0; k < C; ++k) mx = fmaxf(mx, (float)lp[5 + k]);
             den = 0.f;
             for (int k = 0; k < C; ++k) den += expf((float)lp[5 + k] - mx);
@@ -106,7 +132,7 @@ __global__ __launch_bounds__(256) void loss_kernel(
         if (dlogits) {
             T *dp = dlogits + cell_id * ld + a * D;
             const float w_obj = w_best * mb + w_normal * (1.0f - mb);
-            dp[0] = (T)(2.0f * (sg[0] - mb) * w_obj / cnt * sg[0] * (1.0f - sg[0]));
+            dp[0] = ignored ? (T)0.f : (T)(2.0f * (sg[0] - tgt) * w_obj / cnt * sg[0] * (1.0f - sg[0]));
             if constexpr (MODE == Y2_BOX_MSE) {
                 dp[1] = (T)(2.0f * mb * dc0 * w_coords / cnt * sg[1] * (1.0f - sg[1]));
                 dp[2] = (T)(2.0f * mb * dc1 * w_coords / cnt * sg[2] * (1.0f - sg[2]));
@@ -122,14 +148,16 @@ __global__ __launch_bounds__(256) void loss_kernel(
             } else {
                 for (int k = 1; k < 5; ++k) dp[k] = (T)0.f;
             }
-            if (resp) {
-                for (int k = 0; k < C; ++k) {
-                    float p = expf((float)lp[5 + k] - mx) / den;
-                    float d = gp * (p - tp[k]);
-                    dp[5 + k] = (T)(p * (d - dot));
+            if constexpr (CLS == Y2_CLS_MSE) {
+                if (resp) {
+                    for (int k = 0; k < C; ++k) {
+                        float p = expf((float)lp[5 + k] - mx) / den;
+                        float d = gp * (p - tp[k]);
+                        dp[5 + k] = (T)(p * (d - dot));
+                    }
+                } else {
+                    for (int k = 0; k < C; ++k) dp[5 + k] = (T)0.f;
                 }
-            } else {
-                for (int k = 0; k < C; ++k) dp[5 + k] = (T)0.f;
             }
             if (a == 0)
                 for (int k = A * D; k < ld; ++k) dlogits[cell_id * ld + k] = (T)0.f;
@@ -162,12 +190,22 @@ static int lanes_per_cell(int A) {
     return l;
 }
 
+static yolo2_loss_options default_loss_options(int box_loss = Y2_BOX_MSE) {
+    yolo2_loss_options o = {(int)sizeof(yolo2_loss_options), box_loss, Y2_CLS_MSE, 0, 0.0f, 0.0f, 2.0f};
+    return o;
+}
+
 static int loss_impl(const void *logits, int ld, const float *anchors, const float *mask, const float *prob,
                      const float *coords, const float *off_min, const float *off_max, const float *areas,
                      const float *hparam, float *objectives, void *dlogits, float *ws, int B, int cell_h,
-                     int cell_w, int A, int C, int dtype, void *stream, int box_loss = Y2_BOX_MSE) {
+                     int cell_w, int A, int C, int dtype, void *stream, const yolo2_loss_options &o = default_loss_options()) {
     Y2_CHECK_ARG(logits && anchors && mask && prob && coords && off_min && off_max && areas && hparam && ws);
+    const int box_loss = o.box_loss;
     Y2_CHECK_ARG(box_loss >= 0 && box_loss < Y2_BOX_MODES);
+    Y2_CHECK_ARG(o.class_loss >= 0 && o.class_loss < Y2_CLS_MODES && (o.rescore == 0 || o.rescore == 1));
+    Y2_CHECK_ARG(o.ignore_thresh == 0.0f || (o.ignore_thresh > 0.0f && o.ignore_thresh < 1.0f));                 // (a NaN fails both)
+    Y2_CHECK_ARG(o.label_smoothing >= 0.0f && o.label_smoothing < 1.0f && (o.class_loss != Y2_CLS_MSE || o.label_smoothing == 0.0f));
+    Y2_CHECK_ARG(o.class_loss != Y2_CLS_FOCAL || o.focal_gamma == 0.0f || (o.focal_gamma >= 1.0f && std::isfinite(o.focal_gamma)));
     Y2_CHECK_ARG(B > 0 && cell_h > 0 && cell_w > 0 && A > 0 && A <= 64 && C > 0 && ld >= A * (5 + C));
     hipStream_t st = (hipStream_t)stream;
     const int LPC = lanes_per_cell(A);
@@ -176,10 +214,25 @@ static int loss_impl(const void *logits, int ld, const float *anchors, const flo
     float hp[4];
     // hparam is a host pointer: 4 weights {iou_best, iou_normal, coords, prob}
     hp[0] = hparam[0]; hp[1] = hparam[1]; hp[2] = hparam[2]; hp[3] = hparam[3];
-#define Y2_LOSS_LAUNCH(MODE)                                                                                                                     \
-    Y2_DISPATCH_DTYPE(dtype, (loss_kernel<T, MODE><<<nblocks, 256, 0, st>>>((const T *)logits, ld, anchors, mask, prob, coords, off_min, off_max, \
-                                                                            areas, hp[0], hp[1], hp[2], hp[3], (T *)dlogits, ws, B, cell_h,     \
-                                                                            cell_w, A, C, LPC)))
+    // focal with gamma 0 is the cross-entropy; EXT only where the ignore threshold or the IoU target is on: all off is the launch as it was
+    const int cls = o.class_loss == Y2_CLS_FOCAL && o.focal_gamma == 0.0f ? Y2_CLS_CE : o.class_loss;
+    const bool ext = o.ignore_thresh > 0.0f || o.rescore != 0;
+    const loss_opts ko = {o.ignore_thresh, o.rescore, o.label_smoothing, o.focal_gamma};
+#define Y2_LOSS_LAUNCH4(MODE, CLS, EXT)                                                                                                                    \
+    Y2_DISPATCH_DTYPE(dtype, (loss_kernel<T, MODE, CLS, EXT><<<nblocks, 256, 0, st>>>((const T *)logits, ld, anchors, mask, prob, coords, off_min, off_max, \
+                                                                                      areas, hp[0], hp[1], hp[2], hp[3], (T *)dlogits, ws, B, cell_h,     \
+                                                                                      cell_w, A, C, LPC, ko)))
+#define Y2_LOSS_LAUNCH3(MODE, CLS)                 \
+    do {                                           \
+        if (ext) Y2_LOSS_LAUNCH4(MODE, CLS, true); \
+        else Y2_LOSS_LAUNCH4(MODE, CLS, false);    \
+    } while (0)
+#define Y2_LOSS_LAUNCH(MODE)                                           \
+    do {                                                               \
+        if (cls == Y2_CLS_MSE) Y2_LOSS_LAUNCH3(MODE, Y2_CLS_MSE);      \
+        else if (cls == Y2_CLS_CE) Y2_LOSS_LAUNCH3(MODE, Y2_CLS_CE);   \
+        else Y2_LOSS_LAUNCH3(MODE, Y2_CLS_FOCAL);                      \
+    } while (0)
     switch (box_loss) {
         case Y2_BOX_MSE: Y2_LOSS_LAUNCH(Y2_BOX_MSE); break;
         case Y2_BOX_IOU: Y2_LOSS_LAUNCH(Y2_BOX_IOU); break;
@@ -188,6 +241,8 @@ static int loss_impl(const void *logits, int ld, const float *anchors, const flo
         default: Y2_LOSS_LAUNCH(Y2_BOX_CIOU); break;
     }
 #undef Y2_LOSS_LAUNCH
+#undef Y2_LOSS_LAUNCH3
+#undef Y2_LOSS_LAUNCH4
     if (objectives) loss_finalize_kernel<<<1, 256, 0, st>>>(ws, nblocks, (float)((long)B * cell_h * cell_w * A), objectives);
     Y2_CHECK_LAUNCH();
     return YOLO2_OK;
@@ -220,13 +275,31 @@ extern "C" int yolo2_loss_box(const void *logits, int ld, const float *anchors, 
                               const float *hparam, float *objectives, void *dlogits, float *ws, int B, int cell_h,
                               int cell_w, int A, int C, int dtype, void *stream, int box_loss) {
     Y2_CHECK_ARG(objectives);
-    return loss_impl(logits, ld, anchors, mask, prob, coords, off_min, off_max, areas, hparam, objectives, dlogits, ws, B, cell_h, cell_w, A, C, dtype, stream, box_loss);
+    return loss_impl(logits, ld, anchors, mask, prob, coords, off_min, off_max, areas, hparam, objectives, dlogits, ws, B, cell_h, cell_w, A, C, dtype, stream, default_loss_options(box_loss));
 }
 extern "C" int yolo2_loss_box_partials(const void *logits, int ld, const float *anchors, const float *mask, const float *prob,
                                        const float *coords, const float *off_min, const float *off_max, const float *areas,
                                        const float *hparam, void *dlogits, float *ws, int B, int cell_h, int cell_w, int A, int C, int dtype,
                                        void *stream, int box_loss) {
-    return loss_impl(logits, ld, anchors, mask, prob, coords, off_min, off_max, areas, hparam, nullptr, dlogits, ws, B, cell_h, cell_w, A, C, dtype, stream, box_loss);
+    return loss_impl(logits, ld, anchors, mask, prob, coords, off_min, off_max, areas, hparam, nullptr, dlogits, ws, B, cell_h, cell_w, A, C, dtype, stream, default_loss_options(box_loss));
+}
+// One options struct for every loss option (include/yolo2_hip.h: yolo2_loss_options; loss_opts.h); with the defaults these are yolo2_loss /
+// yolo2_loss_partials, with only box_loss set yolo2_loss_box / yolo2_loss_box_partials, bit for bit.  A NULL or differently sized struct and
+// every out-of-range field are argument errors: nothing is launched.
+extern "C" int yolo2_loss_ex(const void *logits, int ld, const float *anchors, const float *mask, const float *prob,
+                             const float *coords, const float *off_min, const float *off_max, const float *areas,
+                             const float *hparam, float *objectives, void *dlogits, float *ws, int B, int cell_h,
+                             int cell_w, int A, int C, int dtype, void *stream, const yolo2_loss_options *opt) {
+    Y2_CHECK_ARG(objectives);
+    Y2_CHECK_ARG(opt && opt->size == (int)sizeof(yolo2_loss_options));
+    return loss_impl(logits, ld, anchors, mask, prob, coords, off_min, off_max, areas, hparam, objectives, dlogits, ws, B, cell_h, cell_w, A, C, dtype, stream, *opt);
+}
+extern "C" int yolo2_loss_ex_partials(const void *logits, int ld, const float *anchors, const float *mask, const float *prob,
+                                      const float *coords, const float *off_min, const float *off_max, const float *areas,
+                                      const float *hparam, void *dlogits, float *ws, int B, int cell_h, int cell_w, int A, int C, int dtype,
+                                      void *stream, const yolo2_loss_options *opt) {
+    Y2_CHECK_ARG(opt && opt->size == (int)sizeof(yolo2_loss_options));
+    return loss_impl(logits, ld, anchors, mask, prob, coords, off_min, off_max, areas, hparam, nullptr, dlogits, ws, B, cell_h, cell_w, A, C, dtype, stream, *opt);
 }
 extern "C" int yolo2_loss_objectives(const float *ws, float *objectives, int B, int cell_h, int cell_w, int A, void *stream) {
     Y2_CHECK_ARG(ws && objectives && B > 0 && cell_h > 0 && cell_w > 0 && A > 0 && A <= 64);

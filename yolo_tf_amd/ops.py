@@ -313,14 +313,49 @@ def box_loss_code(box_loss):
         raise ValueError('box_loss = %r: one of %s' % (box_loss, ', '.join(_lib.BOX_LOSSES)))
 
 
-def loss(logits, ld, anchors, labels, hparam, objectives, dlogits, ws, B, ch, cw, A, C, box_loss='mse'):
+def loss_options(box_loss='mse', class_loss='mse', ignore_thresh=0.0, rescore=False, label_smoothing=0.0, focal_gamma=2.0):
+    """The options of the YOLOv2 loss (DESIGN.md sections 21 and 22) checked on the host: None when only ``box_loss`` may differ from its default
+    (the call made before the other options existed serves), else the ``_lib.LossOptions`` of yolo2_loss_ex.  An unknown name or a value out of
+    range raises ValueError naming the option."""
+    mode = box_loss_code(box_loss)
+    try:
+        cls = _lib.CLASS_LOSSES[class_loss]
+    except (KeyError, TypeError):
+        raise ValueError('class_loss = %r: one of %s' % (class_loss, ', '.join(_lib.CLASS_LOSSES)))
+    try:
+        t, eps, gamma = float(ignore_thresh), float(label_smoothing), float(focal_gamma)
+    except (TypeError, ValueError):
+        raise ValueError('ignore_thresh, label_smoothing and focal_gamma are numbers, not %r, %r, %r' % (ignore_thresh, label_smoothing, focal_gamma))
+    if not (t == 0.0 or 0.0 < t < 1.0):
+        raise ValueError('ignore_thresh = %r: 0 (off) or a threshold inside (0, 1)' % (ignore_thresh,))
+    if rescore not in (False, True, 0, 1):
+        raise ValueError('rescore = %r: True or False' % (rescore,))
+    if not 0.0 <= eps < 1.0:
+        raise ValueError('label_smoothing = %r: lies in [0, 1)' % (label_smoothing,))
+    if eps != 0.0 and cls == 0:
+        raise ValueError('label_smoothing = %r with class_loss mse: smoothing belongs to ce and focal' % (label_smoothing,))
+    if cls == 2 and not (gamma == 0.0 or (1.0 <= gamma < float('inf'))):
+        raise ValueError('focal_gamma = %r: 0 or at least 1' % (focal_gamma,))
+    if cls == 0 and t == 0.0 and not rescore:
+        return None
+    return _lib.LossOptions(ctypes.sizeof(_lib.LossOptions), mode, cls, int(bool(rescore)), t, eps, gamma if cls == 2 else 2.0)
+
+
+def loss(logits, ld, anchors, labels, hparam, objectives, dlogits, ws, B, ch, cw, A, C, box_loss='mse', class_loss='mse', ignore_thresh=0.0,
+         rescore=False, label_smoothing=0.0, focal_gamma=2.0):
     """labels: 6 device f32 tensors (mask, prob, coords, off_min, off_max, areas); hparam: 4 host floats
     in the order iou_best, iou_normal, coords, prob.  ``box_loss``: 'mse' (the reference's squared error, the call made before the option
-    existed) or 'iou' / 'giou' / 'diou' / 'ciou' (DESIGN.md section 21)."""
+    existed) or 'iou' / 'giou' / 'diou' / 'ciou' (DESIGN.md section 21).  ``class_loss`` 'mse' | 'ce' | 'focal' with ``label_smoothing`` and
+    ``focal_gamma``, ``ignore_thresh`` and ``rescore``: DESIGN.md section 22; with all of them at their defaults the call is yolo2_loss or
+    yolo2_loss_box as before, otherwise yolo2_loss_ex."""
     mode = box_loss_code(box_loss)
+    opt = loss_options(box_loss, class_loss, ignore_thresh, rescore, label_smoothing, focal_gamma)
     hp = (ctypes.c_float * 4)(*[float(v) for v in hparam])
     mask, prob, coords, omin, omax, areas = labels
-    if mode == 0:
+    if opt is not None:
+        call('yolo2_loss_ex', ptr(logits), ld, ptr(anchors), ptr(mask), ptr(prob), ptr(coords), ptr(omin), ptr(omax), ptr(areas), hp,
+             ptr(objectives), ptr(dlogits), ptr(ws), B, ch, cw, A, C, dtype_code(logits.dtype), _stream(), ctypes.byref(opt))
+    elif mode == 0:
         call('yolo2_loss', ptr(logits), ld, ptr(anchors), ptr(mask), ptr(prob), ptr(coords), ptr(omin), ptr(omax), ptr(areas), hp,
              ptr(objectives), ptr(dlogits), ptr(ws), B, ch, cw, A, C, dtype_code(logits.dtype), _stream())
     else:
@@ -328,12 +363,17 @@ def loss(logits, ld, anchors, labels, hparam, objectives, dlogits, ws, B, ch, cw
              ptr(objectives), ptr(dlogits), ptr(ws), B, ch, cw, A, C, dtype_code(logits.dtype), _stream(), mode)
 
 
-def loss_partials(logits, ld, anchors, labels, hparam, dlogits, ws, B, ch, cw, A, C, box_loss='mse'):
-    """The loss kernel alone: dlogits + per-workgroup partial sums in ``ws``; ``loss_objectives`` reduces them on demand.  ``box_loss`` as in ``loss``."""
+def loss_partials(logits, ld, anchors, labels, hparam, dlogits, ws, B, ch, cw, A, C, box_loss='mse', class_loss='mse', ignore_thresh=0.0,
+                  rescore=False, label_smoothing=0.0, focal_gamma=2.0):
+    """The loss kernel alone: dlogits + per-workgroup partial sums in ``ws``; ``loss_objectives`` reduces them on demand.  Options as in ``loss``."""
     mode = box_loss_code(box_loss)
+    opt = loss_options(box_loss, class_loss, ignore_thresh, rescore, label_smoothing, focal_gamma)
     hp = (ctypes.c_float * 4)(*[float(v) for v in hparam])
     mask, prob, coords, omin, omax, areas = labels
-    if mode == 0:
+    if opt is not None:
+        call('yolo2_loss_ex_partials', ptr(logits), ld, ptr(anchors), ptr(mask), ptr(prob), ptr(coords), ptr(omin), ptr(omax), ptr(areas), hp,
+             ptr(dlogits), ptr(ws), B, ch, cw, A, C, dtype_code(logits.dtype), _stream(), ctypes.byref(opt))
+    elif mode == 0:
         call('yolo2_loss_partials', ptr(logits), ld, ptr(anchors), ptr(mask), ptr(prob), ptr(coords), ptr(omin), ptr(omax), ptr(areas), hp,
              ptr(dlogits), ptr(ws), B, ch, cw, A, C, dtype_code(logits.dtype), _stream())
     else:

@@ -43,6 +43,57 @@ def box_loss_option(box_loss, config):
     return name
 
 
+CLASS_LOSSES = ('mse', 'ce', 'focal')
+LOSS_OPTION_DEFAULTS = {'box_loss': 'mse', 'class_loss': 'mse', 'ignore_thresh': 0.0, 'rescore': False, 'label_smoothing': 0.0, 'focal_gamma': 2.0}
+
+
+def loss_options(config, box_loss=None, class_loss=None, ignore_thresh=None, rescore=None, label_smoothing=None, focal_gamma=None):
+    """Every option of the YOLOv2 loss of a TrainSession (DESIGN.md sections 21, 22) as the keyword arguments of ``ops.loss``: each argument, or
+    the ``[mi355x]`` key of the same name where the argument is None; absent = off (LOSS_OPTION_DEFAULTS).  An unknown name or a value out of
+    range raises ValueError naming the option.  Pure host logic."""
+    def key(name, given, read):
+        if given is not None:
+            return given
+        if config is not None and config.has_option('mi355x', name):
+            try:
+                return read('mi355x', name)
+            except ValueError:
+                raise ValueError('[mi355x] %s = %r: not a valid value' % (name, config.get('mi355x', name)))
+        return LOSS_OPTION_DEFAULTS[name]
+
+    def number(name, v):
+        try:
+            return float(v)
+        except (TypeError, ValueError):
+            raise ValueError('%s = %r: a number' % (name, v))
+    out = {'box_loss': box_loss_option(box_loss, config)}
+    cls = key('class_loss', class_loss, config.get if config is not None else None)
+    out['class_loss'] = str(cls).strip().lower()
+    if out['class_loss'] not in CLASS_LOSSES:
+        raise ValueError('class_loss = %r: the class term is one of %s (absent: mse)' % (cls, ', '.join(CLASS_LOSSES)))
+    t = number('ignore_thresh', key('ignore_thresh', ignore_thresh, config.getfloat if config is not None else None))
+    if not (t == 0.0 or 0.0 < t < 1.0):
+        raise ValueError('ignore_thresh = %r: the ignore threshold lies inside (0, 1) (0 or absent: off)' % (t,))
+    r = key('rescore', rescore, config.getboolean if config is not None else None)
+    if r not in (False, True, 0, 1):
+        raise ValueError('rescore = %r: true or false' % (r,))
+    eps = number('label_smoothing', key('label_smoothing', label_smoothing, config.getfloat if config is not None else None))
+    if not 0.0 <= eps < 1.0:
+        raise ValueError('label_smoothing = %r: lies in [0, 1) (0 or absent: off)' % (eps,))
+    if eps != 0.0 and out['class_loss'] == 'mse':
+        raise ValueError('label_smoothing = %r with class_loss = mse: smoothing belongs to the ce and focal class terms' % (eps,))
+    gamma = number('focal_gamma', key('focal_gamma', focal_gamma, config.getfloat if config is not None else None))
+    if out['class_loss'] == 'focal' and not (gamma == 0.0 or 1.0 <= gamma < float('inf')):       # (read with focal only, as ops.loss_options and the library do)
+        raise ValueError('focal_gamma = %r: 0 or at least 1 (absent: 2)' % (gamma,))
+    out.update(ignore_thresh=t, rescore=bool(r), label_smoothing=eps, focal_gamma=gamma)
+    return out
+
+
+def loss_options_set(options):
+    """The names of the options of ``loss_options`` that are on, box_loss aside (focal_gamma counts only with the focal class term)."""
+    return [k for k in ('class_loss', 'ignore_thresh', 'rescore', 'label_smoothing') if options[k] != LOSS_OPTION_DEFAULTS[k]]
+
+
 def ema_decay_at(ema_decay, t):
     """[TF-sem] tf.train.ExponentialMovingAverage(decay, num_updates=t): min(decay, (1 + t) / (10 + t)), in Python floats."""
     return min(ema_decay, (1.0 + t) / (10.0 + t))
@@ -55,7 +106,8 @@ class TrainSession(object):
 
     def __init__(self, builder, batch_size, dtype='bf16', optimizer='adam', learning_rate=1e-6, gradient_clip=0.0,
                  config=None, seed=0, world_size=1, bucket_mb=64.0, preprocess_mode=0, sizes=None, grad_dtype='f32', comm_cus=None, comm_timing=False,
-                 sync_bn=False, shard_optimizer=False, deterministic=None, ema_decay=None, box_loss=None):
+                 sync_bn=False, shard_optimizer=False, deterministic=None, ema_decay=None, box_loss=None,
+                 class_loss=None, ignore_thresh=None, rescore=None, label_smoothing=None, focal_gamma=None):
         """``sizes``: optional list of (width, height) input sizes for multi-scale training (BASELINE configs[3]); buffers are
         allocated once for the largest, ``set_size`` switches between them, the builder's configured size is selected first.
 
@@ -68,10 +120,15 @@ class TrainSession(object):
         None (default): ``[mi355x] ema_decay`` of the config; absent or 0: off -- ``session.ema`` is None, nothing is allocated or launched.
 
         ``box_loss``: the box regression term of the YOLOv2 loss: 'mse' (the reference's squared error) or 'iou', 'giou',
-        'diou', 'ciou'.  None (default): ``[mi355x] box_loss`` of the config; absent or 'mse': the loss call made before the option existed."""
+        'diou', 'ciou'.  None (default): ``[mi355x] box_loss`` of the config; absent or 'mse': the loss call made before the option existed.
+
+        ``class_loss`` ('mse' | 'ce' | 'focal'), ``ignore_thresh``, ``rescore``, ``label_smoothing``, ``focal_gamma``: the other options of the
+        YOLOv2 loss.  None (default): the ``[mi355x]`` key of the same name; absent: off, the loss call as it was."""
         assert builder.training, 'call builder(data, training=True) first'
         self.ema_decay = ema_decay_option(ema_decay, config if config is not None else getattr(builder, 'config', None))
-        self.box_loss = box_loss_option(box_loss, config if config is not None else getattr(builder, 'config', None))
+        self.loss_options = loss_options(config if config is not None else getattr(builder, 'config', None), box_loss, class_loss, ignore_thresh,
+                                         rescore, label_smoothing, focal_gamma)
+        self.box_loss = self.loss_options['box_loss']
         self.builder = builder
         self.B = batch_size
         own = (builder.width, builder.height)
@@ -79,6 +136,9 @@ class TrainSession(object):
         self.v1 = getattr(builder, 'family', 'yolo2') == 'yolo'       # YOLO (v1): linear fully connected head, boxes_per_cell instead of anchors
         if self.v1 and self.box_loss != 'mse':
             raise NotImplementedError('box_loss = %s covers the YOLOv2 family: the YOLO (v1) loss regresses its boxes with the squared error only' % self.box_loss)
+        on = loss_options_set(self.loss_options)
+        if self.v1 and on:
+            raise NotImplementedError('%s = %s covers the YOLOv2 family: the YOLO (v1) loss has its own objectness and class terms only' % (on[0], self.loss_options[on[0]]))
         assert not (self.v1 and sizes), 'the fully connected YOLO (v1) head fixes the input size'
         for wh in (sizes or []):
             wh = (int(wh[0]), int(wh[1]))
@@ -201,9 +261,10 @@ class TrainSession(object):
             ops.yolo1_loss(logits, ld, self.labels, self.hparam, self.objectives_dev, dlogits, self.loss_ws, self.B, m.cell_height, m.cell_width, self.A, self.C)
         else:
             # (the four objective values are reduced from the partial sums when fetch() asks for them)
-            # (box_loss 'mse' is yolo2_loss_partials, the call made before the option existed; the other modes take yolo2_loss_box_partials)
+            # (box_loss 'mse' is yolo2_loss_partials, the call made before the option existed; the other modes take yolo2_loss_box_partials,
+            # any option of section 22 yolo2_loss_ex_partials)
             ops.loss_partials(logits, ld, self.anchors, self.labels, self.hparam, dlogits, self.loss_ws, self.B, m.cell_height, m.cell_width, self.A, self.C,
-                              box_loss=self.box_loss)
+                              **self.loss_options)
             self._objectives_pending = (m.cell_height, m.cell_width)
         if self.reducer is not None:
             self.reducer.begin()
