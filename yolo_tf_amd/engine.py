@@ -15,6 +15,7 @@ Memory layout decisions (288 GB HBM: nothing is recomputed, nothing is re-alloca
 """
 import numpy as np
 import os
+from collections import namedtuple
 
 import torch
 
@@ -53,6 +54,145 @@ def layer_end_offsets(graph, offsets):
             names = [op['weights'].name] + [op[k].name for k in ('gamma', 'beta', 'biases') if k in op]
             ends[op['name']] = max(offsets[n][0] + (offsets[n][1] + ARENA_ALIGN - 1) // ARENA_ALIGN * ARENA_ALIGN for n in names)
     return ends
+
+
+Options = namedtuple('Options', 'deterministic sync_bn fuse_pool fold_bn fuse_bn_stats fold_finalize fuse_first fuse_first_wgrad fuse_bn_bwd '
+                                'overlap_wgrad side_priority')
+
+
+def read_options(training, deterministic=False, sync_bn=False, side_priority=-1, env=None):
+    """Every A/B switch the engine honours, with what the deterministic mode, sync-BN and inference impose already applied: read once per
+    engine (the only environment read of this module; ``env``: a mapping to read instead, for tests and scripts/record_engine_plans.py)."""
+    env = os.environ if env is None else env
+    det, sync = bool(deterministic) and training, bool(sync_bn) and training
+
+    def on(name):
+        return env.get(name, '1') != '0'
+    return Options(
+        deterministic=det, sync_bn=sync,
+        fuse_pool=on('YOLO2_FUSE_POOL'),
+        fold_bn=on('YOLO2_FOLD_BN'),
+        fuse_bn_stats=on('YOLO2_FUSE_BN_STATS') and not det,
+        # 0: separate finalisation kernels (A/B).  Sync-BN: the sums have to exist outside a kernel to be exchanged
+        fold_finalize=on('YOLO2_FOLD_FINALIZE') and not sync,
+        # image layer recomputed inside its consumers instead of stored: 'infer' (default: detect only -- batch 256: 12.5 -> 11.3 ms),
+        # '1' (training too: measured neutral, the recomputing backward kernels are VALU-bound -- profiles/r03_first_layer_fused.md), '0' never
+        # (deterministic: the recomputing backward kernels of the image layer leave their sums in wrapped partial rows)
+        fuse_first='infer' if det else env.get('YOLO2_FUSE_FIRST', 'infer'),
+        fuse_first_wgrad=on('YOLO2_FUSE_FIRST_WGRAD') and not det,
+        fuse_bn_bwd=on('YOLO2_FUSE_BN_BWD') and not det,
+        overlap_wgrad=on('YOLO2_OVERLAP_WGRAD'),              # 0: single stream (clean per-kernel profiles)
+        # The filter-gradient stream at HIGH priority (YOLO2_SIDE_PRIORITY=0: normal, A/B).  Both streams' big kernels need a whole CU's LDS and
+        # share the chip workgroup by workgroup; with equal priority the filter gradients fall behind the dependency chain on the main stream and
+        # pile up after its last layer, in front of Adam.  Measured in one call (profiles/r06_new_kernels.txt, last block): 3.470 -> 3.448 ms;
+        # the step on its own (non-default) stream of either priority: 3.50 .. 3.53 ms.
+        # (side_priority: data-parallel sessions pass 0 -- the collective's stream is the one high-priority stream there, as measured in rounds 3-5)
+        side_priority=int(env.get('YOLO2_SIDE_PRIORITY', str(side_priority))))
+
+
+# What one convolution does in a binding, decided from shapes alone:
+#   path         'fold' (inference: BN folded into filter + bias, leaky) | 'first' (image layer recomputed inside its consumers, never stored)
+#                | 'bn' | 'bias_leaky' (YOLO v1) | 'bias'
+#   pool         the stride-2 pool op fused into the layer in both directions, or None
+#   fwd_pool     the pool op the BN pass produces in the forward only (its input has other readers too), or None
+#   stats        batch statistics from the convolution epilogue
+#   fin_limit    most partial rows a reduce_part launch may leave for a *_fin consumer with this many channels (0: none / folded finalisation off)
+#   first_wgrad  filter gradient by the fused image-layer kernel (BN / leaky / pool backward apply inside, reads the pooled gradient)
+#   bn_bwd       the producer conv op whose BN-backward sums this layer's data-gradient epilogue takes, or None
+#   zero         the filter-gradient range must be zero before backward
+LayerPlan = namedtuple('LayerPlan', 'path pool fwd_pool stats fin_limit first_wgrad bn_bwd zero')
+# layers {conv name: LayerPlan}; zero_ranges: merged arena ranges; unstored: tensors the training forward never writes; the last three are
+# the per-layer choices again, keyed as the sweeps over the other ops look them up ({pool input: pool op} twice, {conv name: producer op})
+Plan = namedtuple('Plan', 'layers zero_ranges unstored fused_pool fwd_pool bn_bwd_fused')
+
+
+def plan_binding(graph, batch, dtype, training, opts, pools='all'):
+    """Which path every convolution of ``graph`` takes at this batch size and dtype.  Pure host logic: touches no device and allocates nothing
+    (the library's host queries are asked through ``ops``).  ``pools``: 'all', or 'image' to fuse only the image layer's pool (an engine
+    whose full-resolution activations are read, quant.Calibrator)."""
+    assert pools in ('all', 'image'), pools
+    inputs = set(graph.inputs.values())
+    ld = {t: t.storage()[2] for t in graph.tensors}
+    readers = {}
+    for op in graph.ops:
+        for t in (op.get('inputs') or [op['x']]):
+            readers[t] = readers.get(t, 0) + 1
+    convs = [op for op in graph.ops if op['kind'] == 'conv']
+    producers = {op['out']: op for op in convs}
+    # BN + leaky + max-pool fusion: a batch-normalised conv whose output feeds one stride-2 pool and nothing else never
+    # materialises its full-resolution activation (forward) or that activation's gradient (backward)
+    # forward only: the pool of an activation that has OTHER readers too (Darknet-19's 26x26 passthrough) still comes out of the BN
+    # pass, which then stores both resolutions (yolo2_bn_leaky_pool_fin, A_full); the backward keeps the separate kernels
+    fused_pool, fwd_pool = {}, {}
+    for op in graph.ops if opts.fuse_pool else ():
+        x = op.get('x')
+        if (op['kind'] == 'pool' and op['stride'] == 2 and x in producers and producers[x]['bn'] and x.h % 2 == 0 and x.w % 2 == 0
+                and ld[x] == x.c and ld[op['out']] == op['out'].c and ld[producers[x]['y']] == x.c and x.c // (8 if dtype == torch.bfloat16 else 4) <= 256):
+            if readers[x] > 1:
+                if training:
+                    fwd_pool[x] = op
+            elif pools == 'all' or producers[x]['x'] in inputs:
+                fused_pool[x] = op
+    offsets, _ = layout_params(graph)
+    fin_limits, layers, bn_bwd_fused, unstored, ranges = {}, {}, {}, set(), []
+    for op in convs:
+        x, out, cin, cout, k = op['x'], op['out'], op['cin'], op['cout'], op['ksize']
+        pool = fused_pool.get(out)
+        # The image layer (3 channels in an 8-wide pixel, 32 filters, 3x3, batch-normalised, followed only by a 2x2 pool)
+        image = (op['bn'] and x in inputs and k == 3 and cin <= 8 and ld[x] == 8 and cout == 32 and pool is not None and ld[pool['out']] >= 32
+                 and x.h % 2 == 0 and x.w % 2 == 0)
+        if not training and opts.fold_bn and op['bn'] and pool is None and x not in inputs:
+            # inference-only BN folding applies to batch-normalised layers whose output is a plain activation tensor: not the
+            # image layer (its direct kernel has no bias path) and not a layer fused with its max pool
+            path = 'fold'
+        elif image and cin == 3 and opts.fuse_first != '0' and (not training or (opts.fuse_first == '1' and opts.fuse_bn_stats)):
+            path = 'first'      # takes the recompute-instead-of-store kernels; YOLO2_FUSE_FIRST=0 keeps the stored-output path (A/B, and tests that read the raw output)
+        else:
+            path = 'bn' if op['bn'] else 'bias_leaky' if op['act'] else 'bias'
+        fin_limit = 0
+        if training and op['bn'] and opts.fold_finalize:
+            if cout not in fin_limits:
+                fin_limits[cout] = ops.bn_fin_rows_limit(cout, dtype)
+            fin_limit = fin_limits[cout]
+        # Image layer on the stored-output path: filter gradient with the BN / leaky / pool backward apply inside (YOLO2_FUSE_FIRST_WGRAD=0: the two
+        # launches, A/B).  It reads partial rows, which a pooled layer's reduction leaves for certain from 128 rows on (32 channels: 512 or none)
+        first_wgrad = bool(training and image and path != 'first' and opts.fuse_first_wgrad and ld[pool['out']] % 8 == 0 and fin_limit >= 128
+                           and 'yolo2_first_layer_wgrad_bn' not in _lib.MISSING)
+        # BN-backward sums in the consumer's data-gradient epilogue: a batch-normalised conv whose full-resolution activation has
+        # exactly one reader, a convolution writing that activation's gradient directly (no concat slice, no fan-out)
+        # (measured per layer, profiles/r03_bn_bwd_fusion_per_layer.txt: in a single-stream trace the epilogue sums win 3-10 us per
+        # launch up to 26x26 at batch 16 and lose 1-13 us on the 52x52 / 104x104 layers; with the filter gradients overlapped on the
+        # side stream the whole step is equal either way, so every qualifying layer stays fused)
+        # (round 6: the library's launch rule is asked first -- conv4's data gradient at batch 16 runs plain, its producer's sums come
+        # from the reduction pass that feeds the folded apply pass like every un-fused layer's)
+        bn_bwd = None
+        if (training and opts.fuse_bn_bwd and x in producers and producers[x]['bn'] and readers[x] == 1 and x not in fused_pool
+                and x.storage()[0] not in inputs and ld[x] == x.c and ld[producers[x]['y']] == x.c
+                and ops.conv2d_dgrad_bn_fuses(batch, x.h, x.w, cin, k, dtype)):
+            bn_bwd = bn_bwd_fused[op['name']] = producers[x]
+        # Arena ranges that must be zero before backward: filter gradients that accumulate with atomics (several
+        # pixel ranges per tile; the fused image-layer kernel always adds).  Layers whose filter gradient is a single range store directly
+        # -- at batch 16 those are the three 13x13 layers that hold 70 % of the parameters -- and BN / bias gradients are stored by their
+        # finalisation kernels, so most of the 268 MB arena is never cleared.  Deterministic: every filter gradient is stored by its
+        # reduction launch (yolo2_conv2d_wgrad_ws): nothing accumulates
+        zero = bool(training and not opts.deterministic and (
+            first_wgrad or ops.conv2d_wgrad_accumulates(batch, x.h, x.w, cin, ld[x], cout, pad8(cout), k, dtype)))
+        if zero:
+            off, size = offsets[op['weights'].name]
+            ranges.append((off, off + (size + 3) // 4 * 4))
+        if training and pool is not None:
+            unstored.add(out)
+        if training and path == 'first':
+            unstored.add(op['y'])
+        layers[op['name']] = LayerPlan(path, pool, fwd_pool.get(out), bool(path == 'bn' and training and opts.fuse_bn_stats and ld[op['y']] == cout),
+                                       fin_limit, first_wgrad, bn_bwd, zero)
+    zero_ranges = []
+    for a, b in sorted(ranges):         # merged; bridging small gaps costs less than another launch
+        if zero_ranges and a - zero_ranges[-1][1] <= (1 << 20):
+            zero_ranges[-1] = (zero_ranges[-1][0], max(zero_ranges[-1][1], b))
+        else:
+            zero_ranges.append((a, b))
+    return Plan(layers, zero_ranges, frozenset(unstored), fused_pool, fwd_pool, bn_bwd_fused)
 
 
 _SKEW_KB = 20        # (profiles/r03_arena_stagger.txt)
@@ -109,8 +249,15 @@ class _PartPool(object):
         return None, 0
 
 
+# Unsummed dgamma / dbeta: partial rows [2][rows][C] in ``buf``, planes ``stride`` floats apart; ``part``: the buffer's _PartPool index, -1 for
+# the reduction workspace.  The layer's backward apply pass sums them in its prologue (one launch instead of reduce-finalise + apply).
+_Sums = namedtuple('_Sums', 'buf rows stride part')
+
+
 class Engine(object):
-    def __init__(self, graph, batch_size, dtype='bf16', training=True, seed=0, device=None, sync_bn=False, side_priority=-1, deterministic=False):
+    def __init__(self, graph, batch_size, dtype='bf16', training=True, seed=0, device=None, sync_bn=False, side_priority=-1, deterministic=False,
+                 pools='all'):
+        # ``pools``: which max pools may fuse into their producers, see plan_binding.
         # Deterministic training mode: every float sum of a step has ONE writer per partial and a fixed order.  Filter gradients
         # go through yolo2_conv2d_wgrad_ws, BN statistics and BN-backward sums take the two-launch reduction passes instead of the
         # convolution epilogues' wrapped rows, the image layer's filter gradient is not fused, the library never K-slices.  Decided per
@@ -123,7 +270,6 @@ class Engine(object):
         if not torch.cuda.is_available():
             raise RuntimeError('yolo_tf_amd.Engine needs an MI355X (no CPU path exists)')
         ops._lib.load()
-        self.side_priority = side_priority
         # Synchronised batch normalisation (data-parallel option, [mi355x] sync_bn): batch moments and the BN-backward sums are summed over
         # the replicas, so N ranks x B images train like one process with N x B images.  The reference is single-device (local statistics
         # are what N independent replicas of it would compute; that stays the default).  Costs two small collectives per BN layer and
@@ -135,11 +281,14 @@ class Engine(object):
         self.dtype = _DTYPES[dtype] if isinstance(dtype, str) else dtype
         self.training = training
         self.device = torch.device(device if device is not None else 'cuda:%d' % torch.cuda.current_device())
+        self.opts = o = read_options(training, self.deterministic, self.sync_bn, side_priority)       # every switch, for every binding
+        self.pools = pools
+        self.fuse_bn_stats, self.fuse_first_wgrad, self.fold_finalize = o.fuse_bn_stats, o.fuse_first_wgrad, o.fold_finalize
+        self.overlap_wgrad = o.overlap_wgrad       # a run-time value: bench.py turns it off around its single-stream profile
         self._alloc_variables()
         self._alloc_activations()
         self.init_variables(seed)
         self._filters_dirty = True
-        self._zero_ranges = None
         self.reg_loss = torch.zeros(1, dtype=torch.float64, device=self.device)      # sum of the regularisation terms of the last backward
         self._has_l2 = any(op.get('l2') for op in graph.ops)                         # (only the YOLO v1 family's fully connected layers)
         self.dropout_masks = None    # {op name: uint8 mask}: fixed keep masks (parity tests); None = drawn on the device per step
@@ -241,24 +390,12 @@ class Engine(object):
             max_c = max(max_c, ldy)
         self._bindings = {}
         self._tmp_roots = {}
-        self.fold_finalize = os.environ.get('YOLO2_FOLD_FINALIZE', '1') != '0' and not self.sync_bn
-        self.pool_ymax = self.fold_finalize
         self._bind(self.graph)
-        self.fold_bn = os.environ.get('YOLO2_FOLD_BN', '1') != '0'
-        self.fuse_bn_stats = os.environ.get('YOLO2_FUSE_BN_STATS', '1') != '0' and not self.deterministic
         # Partial rows of the fused statistics ([2][YOLO2_BN_PART_ROWS][C] each).  Producers (convolution epilogues) need a zero buffer; the
         # consumer that finalises the rows in its own prologue only reads them and clears a buffer an EARLIER consumer is done with
-        # (_PartPool below) -- no finalisation launch, no memset launch.  YOLO2_FOLD_FINALIZE=0: separate finalisation kernels (A/B).
+        # (_PartPool below) -- no finalisation launch, no memset launch.
         self.parts = _PartPool(3, 2 * 256 * max(max_c, 8), dev)
-        self.bn_part = self.parts.bufs[0]                       # (kept for callers that drive the two-launch form directly)
-        # image layer recomputed inside its consumers instead of stored: 'infer' (default: detect only -- batch 256: 12.5 -> 11.3 ms),
-        # '1' (training too: measured neutral, the recomputing backward kernels are VALU-bound -- profiles/r03_first_layer_fused.md), '0' never
-        self.fuse_first = os.environ.get('YOLO2_FUSE_FIRST', 'infer')
-        self.fuse_first_wgrad = os.environ.get('YOLO2_FUSE_FIRST_WGRAD', '1') != '0' and not self.deterministic
-        if self.deterministic and self.training:
-            self.fuse_first = 'infer'       # (the recomputing backward kernels of the image layer leave their sums in wrapped partial rows)
-        self._bz_pending = {}                                    # producer layer -> (buffer, rows): BN-backward sums waiting for their apply pass
-        self._fin_rows_limit = {}
+        self._bz_pending = {}                                    # producer layer -> _Sums: BN-backward sums waiting for their apply pass
         # scratch sizes come from the library's own queries (include/yolo2_hip.h yolo2_*_workspace_bytes)
         conv_bytes = 0
         for op in self.graph.ops:
@@ -274,16 +411,8 @@ class Engine(object):
             # (and the following layers' backward) on the main stream, so dY(L) must outlive the next layers' writes
             self.dy_ring = [staggered(max_y, T, dev) for _ in range(3)]
             self.dy_free = [None, None, None]                    # event: the side stream has finished reading that buffer
-            # The filter-gradient stream at HIGH priority (YOLO2_SIDE_PRIORITY=0: normal, A/B).  Both streams' big kernels need a whole CU's LDS and
-            # share the chip workgroup by workgroup; with equal priority the filter gradients fall behind the dependency chain on the main stream and
-            # pile up after its last layer, in front of Adam.  Measured in one call (profiles/r06_new_kernels.txt, last block): 3.470 -> 3.448 ms;
-            # the step on its own (non-default) stream of either priority: 3.50 .. 3.53 ms.
-            # (side_priority: data-parallel sessions pass 0 -- the collective's stream is the one high-priority stream there, as measured in rounds 3-5)
-            prio = int(os.environ.get('YOLO2_SIDE_PRIORITY', str(self.side_priority)))
-            lo, hi = torch.cuda.Stream.priority_range()
-            self.side_stream = torch.cuda.Stream(device=dev, priority=max(min(prio, max(lo, hi)), min(lo, hi)))
-            self.overlap_wgrad = os.environ.get('YOLO2_OVERLAP_WGRAD', '1') != '0'   # 0: single stream (clean per-kernel profiles)
-            self.overlap_max_m = 1 << 40   # A/B: overlap only layers with at most this many output pixels
+            lo, hi = torch.cuda.Stream.priority_range()          # (the filter-gradient stream's priority: read_options)
+            self.side_stream = torch.cuda.Stream(device=dev, priority=max(min(self.opts.side_priority, max(lo, hi)), min(lo, hi)))
             self.wgrad_ws = None           # deterministic mode: slots of the split filter gradients (one buffer: they all run on one stream, in order)
             if self.deterministic:
                 self._alloc_wgrad_ws(self.graph)
@@ -300,80 +429,51 @@ class Engine(object):
             act[t] = (root[off:], ld)
             if r.name in self._groots:
                 gact[t] = (self._groots[r.name][off:], ld)
-        # BN + leaky + max-pool fusion: a batch-normalised conv whose output feeds one stride-2 pool and nothing else never
-        # materialises its full-resolution activation (forward) or that activation's gradient (backward)
-        fused_pool, fwd_pool = {}, {}
-        if os.environ.get('YOLO2_FUSE_POOL', '1') != '0':
-            uses = {}
-            for op in graph.ops:
-                for t in (op.get('inputs') or [op['x']]):
-                    uses[t] = uses.get(t, 0) + 1
-            producers = {op['out']: op for op in graph.ops if op['kind'] == 'conv'}
-            for op in graph.ops:
-                x = op.get('x')
-                if (op['kind'] == 'pool' and op['stride'] == 2 and x in producers and producers[x]['bn'] and uses.get(x, 0) == 1
-                        and x.h % 2 == 0 and x.w % 2 == 0 and act[x][1] == x.c and act[op['out']][1] == op['out'].c
-                        and act[producers[x]['y']][1] == x.c and x.c // (8 if T == torch.bfloat16 else 4) <= 256):
-                    fused_pool[x] = op
-                    st = self.conv[producers[x]['name']]
-                    need = B * (x.h // 2) * (x.w // 2) * x.c
-                    if self.training and ('pool_idx' not in st or st['pool_idx'].numel() < need):
-                        st['pool_idx'] = torch.zeros(need, dtype=torch.uint8, device=dev)
-                    # the raw output AT the arg-max, a quarter of y: all the layer's backward reduction needs
-                    if self.training and self.pool_ymax and ('pool_ymax' not in st or st['pool_ymax'].numel() < need):
-                        st['pool_ymax'] = staggered(need, T, dev)
-            # forward only: the pool of an activation that has OTHER readers too (Darknet-19's 26x26 passthrough) still comes out of the BN
-            # pass, which then stores both resolutions (yolo2_bn_leaky_pool_fin, A_full); the backward keeps the separate kernels
-            for op in graph.ops:
-                x = op.get('x')
-                if (self.training and op['kind'] == 'pool' and op['stride'] == 2 and x in producers and producers[x]['bn'] and x not in fused_pool
-                        and uses.get(x, 0) > 1 and x.h % 2 == 0 and x.w % 2 == 0 and act[x][1] == x.c and act[op['out']][1] == op['out'].c
-                        and act[producers[x]['y']][1] == x.c and x.c // (8 if T == torch.bfloat16 else 4) <= 256
-                        ):
-                    fwd_pool[x] = op
-        # BN-backward sums in the consumer's data-gradient epilogue: a batch-normalised conv whose full-resolution activation has
-        # exactly one reader, a convolution writing that activation's gradient directly (no concat slice, no fan-out)
-        bn_bwd_fused = {}
-        if self.training and os.environ.get('YOLO2_FUSE_BN_BWD', '1') != '0' and not self.deterministic:
-            uses = {}
-            for op in graph.ops:
-                for t in (op.get('inputs') or [op['x']]):
-                    uses[t] = uses.get(t, 0) + 1
-            producers = {op['out']: op for op in graph.ops if op['kind'] == 'conv'}
-            for op in graph.ops:
-                x = op.get('x')
-                # (measured per layer, profiles/r03_bn_bwd_fusion_per_layer.txt: in a single-stream trace the epilogue sums win 3-10 us per
-                # launch up to 26x26 at batch 16 and lose 1-13 us on the 52x52 / 104x104 layers; with the filter gradients overlapped on the
-                # side stream the whole step is equal either way, so every qualifying layer stays fused)
-                # (round 6: the library's launch rule is asked first -- conv4's data gradient at batch 16 runs plain, its producer's sums come
-                # from the reduction pass that feeds the folded apply pass like every un-fused layer's)
-                if (op['kind'] == 'conv' and x in producers and producers[x]['bn'] and 'fold_bias' not in self.conv[producers[x]['name']]
-                        and uses.get(x, 0) == 1 and x not in fused_pool and x in gact and gact[x][1] == x.c and act[producers[x]['y']][1] == x.c
-                        and ops.conv2d_dgrad_bn_fuses(self.B, x.h, x.w, op['cin'], op['ksize'], self.dtype)):
-                    bn_bwd_fused[op['name']] = producers[x]
+        plan = plan_binding(graph, B, T, self.training, self.opts, self.pools)
+        for op in graph.ops:
+            if op['kind'] != 'conv':
+                continue
+            lp, st = plan.layers[op['name']], self.conv[op['name']]
+            if self.training and lp.pool is not None:
+                need = B * (op['out'].h // 2) * (op['out'].w // 2) * op['cout']
+                if 'pool_idx' not in st or st['pool_idx'].numel() < need:
+                    st['pool_idx'] = torch.zeros(need, dtype=torch.uint8, device=dev)
+                # the raw output AT the arg-max, a quarter of y: all the layer's backward reduction needs
+                if self.opts.fold_finalize and ('pool_ymax' not in st or st['pool_ymax'].numel() < need):
+                    st['pool_ymax'] = staggered(need, T, dev)
+            if lp.path == 'fold' and 'fold_w' not in st:
+                # inference: moving statistics folded into the filter (W * gamma/sigma) and a bias (beta - mean*gamma/sigma)
+                st['fold_w'] = torch.empty_like(self.var[op['weights'].name])
+                st['fold_bias'] = torch.empty(op['cout'], dtype=torch.float32, device=dev)
         inp = next(iter(graph.inputs.values()))
-        self._bindings[(inp.h, inp.w)] = {'graph': graph, 'act': act, 'gact': gact, 'fused_pool': fused_pool, 'zero_ranges': None, 'tmp_grad': {},
-                                          'bn_bwd_fused': bn_bwd_fused, 'fwd_pool': fwd_pool}
+        self._bindings[(inp.h, inp.w)] = {'graph': graph, 'act': act, 'gact': gact, 'plan': plan, 'tmp_grad': {}}
         self._use(inp.h, inp.w)
 
     def _use(self, h, w):
-        bnd = self._bindings[(h, w)]
-        self._cur = bnd
-        self.graph, self.act, self.gact, self.fused_pool = bnd['graph'], bnd['act'], bnd['gact'], bnd['fused_pool']
-        self._zero_ranges, self.tmp_grad = bnd['zero_ranges'], bnd['tmp_grad']
-        self.bn_bwd_fused, self.fwd_pool = bnd['bn_bwd_fused'], bnd['fwd_pool']
+        self._cur = bnd = self._bindings[(h, w)]
+        self.graph, self.act, self.gact, self.plan, self.tmp_grad = bnd['graph'], bnd['act'], bnd['gact'], bnd['plan'], bnd['tmp_grad']
+
+    # the current binding's plan under the names its parts had as engine attributes
+    fused_pool = property(lambda self: self.plan.fused_pool)
+    fwd_pool = property(lambda self: self.plan.fwd_pool)
+    bn_bwd_fused = property(lambda self: self.plan.bn_bwd_fused)
+
+    def _first_fused(self, op):
+        return self.plan.layers[op['name']].path == 'first'
+
+    def _plan_grad_zeroing(self):
+        return list(self.plan.zero_ranges)
 
     def add_size(self, graph):
         """Multi-scale training (BASELINE configs[3]): binds another traced input size of the SAME network (same variables, any
         size not larger than the construction-time one) to the same buffers."""
         names = [v.name for v in graph.variables.values()]
         assert names == [v.name for v in self._bindings[next(iter(self._bindings))]['graph'].variables.values()], 'different network'
-        cur = self._cur
+        (inp,) = self.graph.inputs.values()
         self._bind(graph)
         if self.deterministic:
             self._alloc_wgrad_ws(graph)
-        self._cur = cur
-        self._use(*[k for k, v in self._bindings.items() if v is cur][0])
+        self._use(inp.h, inp.w)
 
     def _alloc_wgrad_ws(self, graph):
         """Deterministic mode: one workspace for the slots of the split filter gradients, sized by the library's query for the largest layer over
@@ -406,41 +506,53 @@ class Engine(object):
         self._use(height, width)
 
     # ---------------------------------------------------------------- helpers
-    def _conv(self, P, F, bias, O, H, W, Cp, ldp, Nf, ldo, k, real_k, bn_shift=None, bn_bwd=None):
-        """yolo2_conv2d launch; when a timer is attached, the 3x3 launches that take the 128-wide filter tile (Nf > 64:
+    def _timer(self, H, W, Nf, k, real_k):
+        """When a timer is attached, the 3x3 convolution launches that take the 128-wide filter tile (Nf > 64:
         conv_igemm_kernel<.., KS = 3, ..>, the kernel that carries 64 % of the training FLOPs; the filter gradient carries
         most of the rest) are bracketed by HIP events; the 1x1 launches are tagged separately.
-        ``real_k`` = unpadded reduction length, for the algorithmic FLOP count."""
+        ``real_k`` = unpadded reduction length, for the algorithmic FLOP count.  -> the started timer (the caller stops it), or None"""
         t = self.kernel_timer if Nf > 64 else None
         if t is not None:
             t.start(2.0 * self.B * H * W * Nf * real_k, self._phase if k == 3 else '1x1')
-        pending = False
-        part = None
-        if bn_shift is not None:     # training forward of a batch-normalised layer: statistics from the conv epilogue
-            part = self.parts.acquire(2 * 256 * Nf)
-            ops.conv2d_bn(P, F, O, self.conv_ws, self.B, H, W, Cp, ldp, Nf, ldo, k, bn_shift, self.parts.bufs[part])
-        elif bn_bwd is not None:     # data gradient + the producer layer's dgamma / dbeta sums from the same epilogue
-            y, mean, var, gamma, beta, dgam, dbet = bn_bwd
-            part = self.parts.acquire(2 * 256 * Nf)
-            pending = ops.conv2d_dgrad_bn(P, F, O, self.conv_ws, self.B, H, W, Cp, ldp, Nf, ldo, k, y, mean, var, gamma, beta, dgam, dbet,
-                                          self.parts.bufs[part], self.ws, BN_EPS, LEAKY_ALPHA)
-        else:
-            ops.conv2d_ws(P, F, bias, O, self.conv_ws, self.B, H, W, Cp, ldp, Nf, ldo, k)
+        return t
+
+    def _conv(self, P, F, bias, O, H, W, Cp, ldp, Nf, ldo, k, real_k):
+        """yolo2_conv2d launch."""
+        t = self._timer(H, W, Nf, k, real_k)
+        ops.conv2d_ws(P, F, bias, O, self.conv_ws, self.B, H, W, Cp, ldp, Nf, ldo, k)
         if t is not None:
             t.stop()
-        if bn_bwd is not None:
-            if not pending:          # the two-step form ran inside the call: the buffer was not touched
-                self.parts.dirty[part] = 0
-                self.parts.consumed(part)
-                return None
-            rows = ops.last_bn_part_rows()
-            if self.fold_finalize and ops.bn_fin_supported(rows, Nf, self.dtype):
-                return part, rows    # the producer layer's backward apply pass sums the rows itself
-            ops.bn_part_to_grads(self.parts.bufs[part], Nf, bn_bwd[5], bn_bwd[6])      # (reads and clears all rows)
-            self.parts.consumed(part, cleared=True)
+
+    def _conv_stats(self, P, F, O, H, W, Cp, ldp, Nf, ldo, k, real_k, shift):
+        """Training forward of a batch-normalised layer: statistics from the conv epilogue.  -> (partial-row buffer index, rows)"""
+        t = self._timer(H, W, Nf, k, real_k)
+        part = self.parts.acquire(2 * 256 * Nf)
+        ops.conv2d_bn(P, F, O, self.conv_ws, self.B, H, W, Cp, ldp, Nf, ldo, k, shift, self.parts.bufs[part])
+        if t is not None:
+            t.stop()
+        return part, ops.last_bn_part_rows()
+
+    def _conv_dgrad_bn(self, P, F, O, H, W, Cp, ldp, Nf, ldo, k, real_k, prod):
+        """Data gradient + the producer layer's dgamma / dbeta sums from the same epilogue.  -> the _Sums the producer's backward apply pass
+        has to sum itself, or None: dgamma / dbeta are final."""
+        pst = self.conv[prod['name']]
+        dgam, dbet = self.gvar[prod['gamma'].name], self.gvar[prod['beta'].name]
+        t = self._timer(H, W, Nf, k, real_k)
+        part = self.parts.acquire(2 * 256 * Nf)
+        pending = ops.conv2d_dgrad_bn(P, F, O, self.conv_ws, self.B, H, W, Cp, ldp, Nf, ldo, k, self.act[prod['y']][0], pst['mean'], pst['var'],
+                                      self.var[prod['gamma'].name], self.var[prod['beta'].name], dgam, dbet,
+                                      self.parts.bufs[part], self.ws, BN_EPS, LEAKY_ALPHA)
+        if t is not None:
+            t.stop()
+        if not pending:          # the two-step form ran inside the call: the buffer was not touched
+            self.parts.dirty[part] = 0
+            self.parts.consumed(part)
             return None
-        if bn_shift is not None:
-            return part, ops.last_bn_part_rows()
+        rows = ops.last_bn_part_rows()
+        if self.opts.fold_finalize and ops.bn_fin_supported(rows, Nf, self.dtype):
+            return _Sums(self.parts.bufs[part], rows, 256 * Nf, part)
+        ops.bn_part_to_grads(self.parts.bufs[part], Nf, dgam, dbet)      # (reads and clears all rows)
+        self.parts.consumed(part, cleared=True)
         return None
 
     def _prepare_filters(self):
@@ -449,7 +561,7 @@ class Engine(object):
             return
         self._filter_descs()
         for op in self.graph.ops:
-            if op['kind'] == 'conv' and 'fold_w' in self.conv[op['name']]:
+            if op['kind'] == 'conv' and self.plan.layers[op['name']].path == 'fold':
                 st = self.conv[op['name']]
                 ops.bn_fold(self.var[op['weights'].name], self.var[op['gamma'].name], self.var[op['beta'].name], self.var[op['moving_mean'].name],
                             self.var[op['moving_variance'].name], st['fold_w'], st['fold_bias'], op['ksize'] ** 2 * op['cin'], op['cout'], BN_EPS)
@@ -467,11 +579,7 @@ class Engine(object):
         for d, op in zip(arr, convs):
             st = self.conv[op['name']]
             k, ldcin, ldcout = op['ksize'], pad8(op['cin']), pad8(op['cout'])
-            if self._folds(op):
-                # inference: moving statistics folded into the filter (W * gamma/sigma) and a bias (beta - mean*gamma/sigma)
-                st['fold_w'] = torch.empty_like(self.var[op['weights'].name])
-                st['fold_bias'] = torch.empty(op['cout'], dtype=torch.float32, device=self.device)
-            d.W = (st['fold_w'] if 'fold_w' in st else self.var[op['weights'].name]).data_ptr()
+            d.W = (st['fold_w'] if self.plan.layers[op['name']].path == 'fold' else self.var[op['weights'].name]).data_ptr()
             d.Ffwd = st['Ffwd'].data_ptr()
             d.Fdgr = st['Fdgr'].data_ptr() if 'Fdgr' in st else None
             d.ksize, d.cin, d.ldcin, d.cout, d.ldcout, d.first_block = k, op['cin'], ldcin, op['cout'], ldcout, first
@@ -516,12 +624,6 @@ class Engine(object):
         ops.adam_filter_prep(self._fdesc, 0, 0, self._small, self._n_small, self.params, self.grads, m, v, alpha, beta1, beta2, eps, gscale, self.dtype)
         self._filters_dirty = False
 
-    def _folds(self, op):
-        """Inference-only BN folding applies to batch-normalised layers whose output is a plain activation tensor: not the
-        image layer (its direct kernel has no bias path) and not a layer fused with its max pool."""
-        return (not self.training and self.fold_bn and op['bn'] and op['out'] not in self.fused_pool
-                and op['x'] not in self.graph.inputs.values())
-
     def set_images(self, images, mode=0):
         """images: f32 [B,H,W,3] device tensor (0..255 for mode 0/1).  mode 0 = per_image_standardization
         (train.py:103 / detect.py `std`), 1 = /255 (detect.py `darknet`), 2 = already preprocessed."""
@@ -530,45 +632,9 @@ class Engine(object):
         self.img = images.contiguous()
         ops.image_prep(self.img, self.act[inp][0], self.ws, self.B, inp.h * inp.w, mode)
 
-    def _plan_grad_zeroing(self):
-        """Arena ranges that must be zero before backward: filter gradients that accumulate with atomics (several
-        pixel ranges per tile).  Layers whose filter gradient is a single range store directly -- at batch 16 those are
-        the three 13x13 layers that hold 70 % of the parameters -- and BN / bias gradients are stored by their
-        finalisation kernels, so most of the 268 MB arena is never cleared."""
-        if False:        # (debugging aid: clear the whole gradient arena every step)
-            return [(0, self.n_params)]
-        if self.deterministic:       # every filter gradient is stored by its reduction launch (yolo2_conv2d_wgrad_ws): nothing accumulates
-            return []
-        ranges = []
-        for op in self.graph.ops:
-            if op['kind'] != 'conv':
-                continue
-            x, out = op['x'], op['out']
-            ldx, ldy = self.act[x][1], pad8(op['cout'])
-            if ops.conv2d_wgrad_accumulates(self.B, x.h, x.w, op['cin'], ldx, op['cout'], ldy, op['ksize'], self.dtype):
-                off, size = self.param_offsets[op['weights'].name]
-                ranges.append((off, off + (size + 3) // 4 * 4))
-        ranges.sort()
-        merged = []
-        for a, b in ranges:
-            if merged and a <= merged[-1][1]:
-                merged[-1] = (merged[-1][0], max(merged[-1][1], b))
-            else:
-                merged.append((a, b))
-        # bridging small gaps costs less than another launch
-        out = []
-        for a, b in merged:
-            if out and a - out[-1][1] <= (1 << 20):
-                out[-1] = (out[-1][0], b)
-            else:
-                out.append((a, b))
-        return out
-
     def zero_grads(self):
-        if self._zero_ranges is None:
-            self._zero_ranges = self._cur['zero_ranges'] = self._plan_grad_zeroing()
-        if self._zero_ranges:
-            ops.zero_ranges(self.grads, self._zero_ranges)
+        if self.plan.zero_ranges:
+            ops.zero_ranges(self.grads, self.plan.zero_ranges)
 
     # ---------------------------------------------------------------- forward
     def forward(self):
@@ -588,15 +654,16 @@ class Engine(object):
                 xb, ldx = self.act[x]
                 st = self.conv[op['name']]
                 M = B * out.h * out.w
-                if op['bn'] and 'fold_bias' in st:
+                lp = self.plan.layers[op['name']]
+                pool = lp.pool
+                if lp.path == 'fold':
                     ob, ldo = self.act[out]
                     ops.conv2d_bias_leaky(xb, st['Ffwd'], st['fold_bias'], ob, self.conv_ws, B, x.h, x.w, pad8(x.c), ldx, op['cout'], ldo, op['ksize'], LEAKY_ALPHA)
-                elif op['bn'] and self._first_fused(op):
+                elif lp.path == 'first':
                     # image layer: its raw output (the largest tensor of the network) is never stored; the statistics pass and the
                     # BN + leaky + pool pass each recompute it from the image (csrc/conv_first.hip: conv_first_pool_kernel)
                     gamma, beta = self.var[op['gamma'].name], self.var[op['beta'].name]
                     mmean, mvar = self.var[op['moving_mean'].name], self.var[op['moving_variance'].name]
-                    pool = self.fused_pool[out]
                     pb, ldp = self.act[pool['out']]
                     if self.training:
                         part = self.parts.acquire(2 * 256 * 32)
@@ -609,47 +676,41 @@ class Engine(object):
                         mean, var = mmean, mvar
                     ops.first_layer_bn_leaky_pool(xb, st['Ffwd'], mean, var, gamma, beta, pb, st.get('pool_idx') if self.training else None,
                                                   B, x.h, x.w, ldp, BN_EPS, LEAKY_ALPHA)
-                elif op['bn']:
+                elif lp.path == 'bn':
                     yb, ldy = self.act[op['y']]
                     gamma, beta = self.var[op['gamma'].name], self.var[op['beta'].name]
                     mmean, mvar = self.var[op['moving_mean'].name], self.var[op['moving_variance'].name]
-                    fused = self.training and self.fuse_bn_stats and ldy == op['cout']
                     shift = self.svar[op['moving_mean'].name]       # the moving mean as of the start of this step (read-only during the step)
-                    produced = self._conv(xb, st['Ffwd'], None, yb, x.h, x.w, pad8(x.c), ldx, op['cout'], ldy, op['ksize'], op['ksize'] ** 2 * op['cin'],
-                                          bn_shift=shift if fused else None)
-                    fin = None
-                    if fused:
+                    conv = (xb, st['Ffwd'], yb, x.h, x.w, pad8(x.c), ldx, op['cout'], ldy, op['ksize'], op['ksize'] ** 2 * op['cin'])
+                    mean, var = (st['mean'], st['var']) if self.training else (mmean, mvar)
+                    fin = False
+                    if lp.stats:
                         # batch moments from the partial sums the convolution left behind (shift = the moving mean)
-                        part, rows = produced
-                        if self.fold_finalize and ops.bn_fin_supported(rows, op['cout'], self.dtype):
-                            fin = (part, rows)              # ... summed by the BN-apply kernel below, in its prologue
-                        else:
+                        part, rows = self._conv_stats(*conv, shift)
+                        fin = self.opts.fold_finalize and ops.bn_fin_supported(rows, op['cout'], self.dtype)
+                        if not fin:         # (else: summed by the BN-apply kernel below, in its prologue)
                             if self.sync_bn and self.bn_world > 1:
                                 self._sync_bn_sums(self.parts.bufs[part], op['cout'])
                             ops.bn_finalize(self.parts.bufs[part], shift, M * (self.bn_world if self.sync_bn else 1), op['cout'], st['mean'], st['var'],
                                             mmean, mvar, BN_DECAY)
                             self.parts.consumed(part, cleared=True)
-                        mean, var = st['mean'], st['var']
-                    elif self.training:
-                        assert not (self.sync_bn and self.bn_world > 1), 'sync_bn needs the statistics from the convolution epilogue (YOLO2_FUSE_BN_STATS=1, dense output)'
-                        ops.bn_stats_ema(yb, st['mean'], st['var'], mmean, mvar, BN_DECAY, self.ws, M, op['cout'])
-                        mean, var = st['mean'], st['var']
                     else:
-                        mean, var = mmean, mvar
-                    pool = self.fused_pool.get(out)
-                    if fin is not None:
-                        part, rows = fin
+                        self._conv(conv[0], conv[1], None, *conv[2:])
+                        if self.training:
+                            assert not (self.sync_bn and self.bn_world > 1), 'sync_bn needs the statistics from the convolution epilogue (YOLO2_FUSE_BN_STATS=1, dense output)'
+                            ops.bn_stats_ema(yb, st['mean'], st['var'], mmean, mvar, BN_DECAY, self.ws, M, op['cout'])
+                    if fin:
                         zbuf, zn = self.parts.take_to_zero(part)
                         if pool is not None:
                             pb, ldp = self.act[pool['out']]
                             ops.bn_leaky_pool_fin(yb, self.parts.bufs[part], rows, shift, mean, var, mmean, mvar, BN_DECAY, gamma, beta, pb, st.get('pool_idx'),
                                                   B, out.h, out.w, op['cout'], ldp, BN_EPS, LEAKY_ALPHA, zbuf, zn, ymax=st.get('pool_ymax'))
                             st['ymax_valid'] = 'pool_ymax' in st
-                        elif out in self.fwd_pool:        # both resolutions from one pass (the activation has a second reader)
-                            pb, ldp = self.act[self.fwd_pool[out]['out']]
+                        elif lp.fwd_pool is not None:     # both resolutions from one pass (the activation has a second reader)
+                            pb, ldp = self.act[lp.fwd_pool['out']]
                             ops.bn_leaky_pool_fin(yb, self.parts.bufs[part], rows, shift, mean, var, mmean, mvar, BN_DECAY, gamma, beta, pb, None,
                                                   B, out.h, out.w, op['cout'], ldp, BN_EPS, LEAKY_ALPHA, zbuf, zn, a_full=self.act[out][0])
-                            pooled.add(self.fwd_pool[out]['name'])
+                            pooled.add(lp.fwd_pool['name'])
                         else:
                             ob, ldo = self.act[out]
                             ops.bn_leaky_fin(yb, self.parts.bufs[part], rows, shift, mean, var, mmean, mvar, BN_DECAY, gamma, beta, ob, M, op['cout'], ldo,
@@ -662,7 +723,7 @@ class Engine(object):
                     else:
                         ob, ldo = self.act[out]
                         ops.bn_leaky(yb, mean, var, gamma, beta, ob, M, op['cout'], ldo, BN_EPS, LEAKY_ALPHA)
-                elif op['act']:
+                elif lp.path == 'bias_leaky':
                     # un-normalised layer of the YOLO (v1) family: conv / fully connected + biases + leaky_relu in one launch
                     ob, ldo = self.act[out]
                     ops.conv2d_bias_leaky(xb, st['Ffwd'], self.var[op['biases'].name], ob, self.conv_ws, B, x.h, x.w, pad8(x.c), ldx, op['cout'], ldo, op['ksize'], LEAKY_ALPHA)
@@ -732,27 +793,31 @@ class Engine(object):
         main = torch.cuda.current_stream()
         side = self.side_stream if self.overlap_wgrad else None
         slot = 0
+
+        def next_dy():
+            """The dY ring's next buffer, once the filter gradient that last read it is done."""
+            nonlocal slot
+            slot = (slot + 1) % 3
+            if self.dy_free[slot] is not None:
+                main.wait_event(self.dy_free[slot])
+            return self.dy_ring[slot]
         for op in reversed(self.graph.ops):
             kind = op['kind']
             if kind == 'conv':
                 x, out = op['x'], op['out']
                 st = self.conv[op['name']]
+                lp = self.plan.layers[op['name']]
                 M = B * out.h * out.w
                 cout, k = op['cout'], op['ksize']
                 ldy = pad8(cout)
-                wgrad_done = False
                 gob, ldgo = self.gact[out]
                 xb, ldx = self.act[x]
                 if op['bn']:
                     yb, _ = self.act[op['y']]
                     gamma, beta = self.var[op['gamma'].name], self.var[op['beta'].name]
                     dgam, dbet = self.gvar[op['gamma'].name], self.gvar[op['beta'].name]
-                    pool = self.fused_pool.get(out)
-                    # ``pfin`` = (partial rows [2][rows][cout], rows, plane stride): dgamma / dbeta are still unsummed and the apply pass
-                    # below sums them in its prologue (one launch instead of reduce-finalise + apply)
-                    pfin = None
-                    limit = self._fin_limit(cout) if self.fold_finalize else 0
-                    first = self._first_fused(op)
+                    pool, limit, first = lp.pool, lp.fin_limit, lp.path == 'first'
+                    pfin = None               # _Sums when dgamma / dbeta are still unsummed
                     if first:                 # image layer: y is recomputed from the image inside both backward kernels
                         dpb, lddp = self.gact[pool['out']]
                         part = self.parts.acquire(2 * 256 * 32)
@@ -766,48 +831,43 @@ class Engine(object):
                             # only arg-max positions carry gradient: the sums over (dP, y at the arg-max) ARE the layer's sums
                             rows = ops.bn_leaky_bwd_reduce_part(dpb, lddp, st['pool_ymax'], st['mean'], st['var'], gamma, beta, self.ws, limit,
                                                                 M // 4, cout, BN_EPS, LEAKY_ALPHA)
-                            pfin = (self.ws, rows, rows * cout)
+                            pfin = _Sums(self.ws, rows, rows * cout, -1)
                         elif limit >= 128:
                             rows = ops.bn_leaky_pool_bwd_reduce_part(dpb, lddp, st['pool_idx'], yb, st['mean'], st['var'], gamma, beta, self.ws, limit,
                                                                      B, out.h, out.w, cout, BN_EPS, LEAKY_ALPHA)
-                            pfin = (self.ws, rows, rows * cout)
+                            pfin = _Sums(self.ws, rows, rows * cout, -1)
                         else:
                             ops.bn_leaky_pool_bwd_reduce(dpb, lddp, st['pool_idx'], yb, st['mean'], st['var'], gamma, beta, dgam, dbet, self.ws,
                                                          B, out.h, out.w, cout, BN_EPS, LEAKY_ALPHA)
                     elif op['name'] in reduced:
-                        pend = self._bz_pending.pop(op['name'], None)      # sums from the consumer's data-gradient epilogue
-                        if pend is not None:
-                            pfin = (self.parts.bufs[pend[0]], pend[1], 256 * cout, pend[0])
+                        pfin = self._bz_pending.pop(op['name'], None)      # sums from the consumer's data-gradient epilogue
                     elif limit >= 64:
                         rows = ops.bn_leaky_bwd_reduce_part(gob, ldgo, yb, st['mean'], st['var'], gamma, beta, self.ws, limit, M, cout, BN_EPS, LEAKY_ALPHA)
-                        pfin = (self.ws, rows, rows * cout)
+                        pfin = _Sums(self.ws, rows, rows * cout, -1)
                     else:
                         ops.bn_leaky_bwd_reduce(gob, ldgo, yb, st['mean'], st['var'], gamma, beta, dgam, dbet, self.ws, M, cout, BN_EPS, LEAKY_ALPHA)
-                    slot = (slot + 1) % 3
-                    dy = self.dy_ring[slot]
-                    if self.dy_free[slot] is not None:
-                        main.wait_event(self.dy_free[slot])       # the filter gradient that last read this buffer is done
+                    # (the fused image-layer filter gradient reads the pooled gradient itself: no dY, no ring buffer -- the layer is the sweep's last)
+                    dy = None if lp.first_wgrad else next_dy()
+                    assert dy is not None or pfin is not None        # (first_wgrad implies fin_limit >= 128: the reduction above left rows)
                     if first:
                         ops.first_layer_pool_bwd_apply(xb, st['Ffwd'], dpb, lddp, st['pool_idx'], st['mean'], st['var'], gamma, beta, dgam, dbet, dy,
                                                        B, x.h, x.w, BN_EPS, LEAKY_ALPHA)
                     elif pfin is not None:
-                        own = pfin[3] if len(pfin) > 3 else -1
-                        zbuf, zn = self.parts.take_to_zero(own)
-                        if pool is not None and self._first_wgrad_fused(op, lddp):
+                        zbuf, zn = self.parts.take_to_zero(pfin.part)
+                        if lp.first_wgrad:
                             # image layer, stored-output path: the BN / leaky / pool backward apply runs inside the filter gradient (its 177 MB output
                             # gradient had one reader; csrc/conv_first.hip conv_first_wgrad_bn_kernel)
-                            ops.first_layer_wgrad_bn(xb, yb, dpb, lddp, st['pool_idx'], st['mean'], st['var'], gamma, beta, pfin[0], pfin[1], pfin[2],
+                            ops.first_layer_wgrad_bn(xb, yb, dpb, lddp, st['pool_idx'], st['mean'], st['var'], gamma, beta, pfin.buf, pfin.rows, pfin.stride,
                                                      dgam, dbet, self.gvar[op['weights'].name], B, x.h, x.w, op['cin'], BN_EPS, LEAKY_ALPHA, zbuf, zn)
                             self._l2(op)
-                            wgrad_done = True
                         elif pool is not None:
-                            ops.bn_leaky_pool_bwd_apply_fin(dpb, lddp, st['pool_idx'], yb, st['mean'], st['var'], gamma, beta, pfin[0], pfin[1], pfin[2],
+                            ops.bn_leaky_pool_bwd_apply_fin(dpb, lddp, st['pool_idx'], yb, st['mean'], st['var'], gamma, beta, pfin.buf, pfin.rows, pfin.stride,
                                                             dgam, dbet, dy, B, out.h, out.w, cout, BN_EPS, LEAKY_ALPHA, zbuf, zn)
                         else:
-                            ops.bn_leaky_bwd_apply_fin(gob, ldgo, yb, st['mean'], st['var'], gamma, beta, pfin[0], pfin[1], pfin[2], dgam, dbet, dy,
+                            ops.bn_leaky_bwd_apply_fin(gob, ldgo, yb, st['mean'], st['var'], gamma, beta, pfin.buf, pfin.rows, pfin.stride, dgam, dbet, dy,
                                                        M, cout, BN_EPS, LEAKY_ALPHA, zbuf, zn)
-                        if own >= 0:
-                            self.parts.consumed(own)
+                        if pfin.part >= 0:
+                            self.parts.consumed(pfin.part)
                     elif pool is not None:
                         ag, ab = self._sync_bn_grads(dgam, dbet, cout)
                         ops.bn_leaky_pool_bwd_apply(dpb, lddp, st['pool_idx'], yb, st['mean'], st['var'], gamma, beta, ag, ab, dy,
@@ -819,10 +879,7 @@ class Engine(object):
                 elif op['act']:
                     # un-normalised layer + leaky_relu (YOLO v1): dZ from the layer's output sign, then the biased-layer path
                     assert ldgo == ldy and self.act[out][1] == ldy
-                    slot = (slot + 1) % 3
-                    dy = self.dy_ring[slot]
-                    if self.dy_free[slot] is not None:
-                        main.wait_event(self.dy_free[slot])
+                    dy = next_dy()
                     ops.leaky_bwd(self.act[out][0], gob, dy, M * ldy, LEAKY_ALPHA)
                     ops.bias_grad(dy, ldy, self.gvar[op['biases'].name], self.ws, M, cout)
                     ring = True
@@ -832,9 +889,9 @@ class Engine(object):
                     ops.bias_grad(dy, ldy, self.gvar[op['biases'].name], self.ws, M, cout)
                     ring = False
                 done = None
-                if wgrad_done:
-                    pass
-                elif side is not None and M <= self.overlap_max_m:
+                if lp.first_wgrad:
+                    pass                             # launched above, inside the BN backward
+                elif side is not None:
                     ready = torch.cuda.Event()
                     ready.record(main)
                     side.wait_event(ready)
@@ -849,13 +906,10 @@ class Engine(object):
                     self._wgrad(xb, dy, self.gvar[op['weights'].name], B, x.h, x.w, op['cin'], ldx, cout, ldy, k)
                     self._l2(op)
                 if x not in inputs:
-                    prod = self.bn_bwd_fused.get(op['name'])
+                    prod = lp.bn_bwd
                     dst, ldd, fin = self._grad_sink(x, written)
                     if prod is not None and fin is None:
-                        pst = self.conv[prod['name']]
-                        pend = self._conv(dy, st['Fdgr'], None, dst, x.h, x.w, ldy, ldy, op['cin'], ldd, k, k * k * cout,
-                                          bn_bwd=(self.act[prod['y']][0], pst['mean'], pst['var'], self.var[prod['gamma'].name], self.var[prod['beta'].name],
-                                                  self.gvar[prod['gamma'].name], self.gvar[prod['beta'].name]))
+                        pend = self._conv_dgrad_bn(dy, st['Fdgr'], dst, x.h, x.w, ldy, ldy, op['cin'], ldd, k, k * k * cout, prod)
                         reduced.add(prod['name'])
                         if pend is not None:
                             self._bz_pending[prod['name']] = pend
@@ -931,31 +985,6 @@ class Engine(object):
             buf = self._bn_sync = torch.zeros(max(n, 4096), dtype=torch.float32, device=self.device)
         return buf[:n]
 
-    def _first_fused(self, op):
-        """The image layer (3 channels in an 8-wide pixel, 32 filters, 3x3, batch-normalised, followed only by a 2x2 pool) takes the
-        recompute-instead-of-store kernels; YOLO2_FUSE_FIRST=0 keeps the stored-output path (A/B, and tests that read the raw output)."""
-        if self.fuse_first == '0' or (self.training and self.fuse_first != '1'):
-            return False
-        x, out = op['x'], op['out']
-        return (op['bn'] and x in self.graph.inputs.values() and op['ksize'] == 3 and op['cin'] == 3 and self.act[x][1] == 8 and op['cout'] == 32
-                and out in self.fused_pool and self.act[self.fused_pool[out]['out']][1] >= 32 and x.h % 2 == 0 and x.w % 2 == 0
-                and (not self.training or self.fuse_bn_stats))
-
-    def _first_wgrad_fused(self, op, lddp):
-        """Image layer on the stored-output path: filter gradient with the BN / leaky / pool backward apply inside (YOLO2_FUSE_FIRST_WGRAD=0: the two
-        launches, A/B)."""
-        x, out = op['x'], op['out']
-        return (self.fuse_first_wgrad and op['bn'] and x in self.graph.inputs.values() and op['ksize'] == 3 and op['cin'] <= 8 and self.act[x][1] == 8
-                and op['cout'] == 32 and out in self.fused_pool and lddp >= 32 and lddp % 8 == 0 and x.h % 2 == 0 and x.w % 2 == 0
-                and 'yolo2_first_layer_wgrad_bn' not in _lib.MISSING)
-
-    def _fin_limit(self, C):
-        """Most partial rows a reduce_part launch may leave for a *_fin consumer with C channels (0: the shape does not qualify)."""
-        v = self._fin_rows_limit.get(C)
-        if v is None:
-            v = self._fin_rows_limit[C] = ops.bn_fin_rows_limit(C, self.dtype)
-        return v
-
     def _l2(self, op):
         """slim.l2_regularizer on a layer's weights (YOLO v1 fully connected layers): gradient and loss term, on the stream of the
         filter gradient it follows."""
@@ -989,18 +1018,11 @@ class Engine(object):
         written), the image layer's raw output when its consumers recompute it.  ``buffer`` is a view of the root buffer starting at the
         tensor's first channel: ``rows`` pixels of ``c`` values every ``ld`` elements (lanes c .. ld-1 are padding or a concat neighbour)."""
         assert self.training, 'the summaries describe a training step'
-        skipped = set()
-        for op in self.graph.ops:
-            if op['kind'] == 'conv' and op['bn']:
-                if op['out'] in self.fused_pool:
-                    skipped.add(op['out'])
-                if self._first_fused(op):
-                    skipped.add(op['y'])
         out = []
         for t in self.graph.tensors:
             if t.flat_of is not None:
                 continue                     # the same bytes as the tensor it re-reads
-            if t in skipped:
+            if t in self.plan.unstored:
                 out.append((t, None))
             else:
                 buf, ld = self.act[t]

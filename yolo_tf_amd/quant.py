@@ -288,10 +288,8 @@ class Calibrator(object):
         if not isinstance(src, Engine):
             raise TypeError('calibration runs on a bf16 / f32 DetectSession')
         self.plan = QuantPlan(src.graph)
-        self.engine = e = Engine(src.graph, src.B, 'bf16', training=False, device=src.device)
+        self.engine = e = Engine(src.graph, src.B, 'bf16', training=False, device=src.device, pools='image')
         e.set_variables(src.get_variables())
-        keep = {t: p for t, p in e.fused_pool.items() if t is self.plan.first_conv['out']}
-        e.fused_pool = e._cur['fused_pool'] = keep
         jobs = []
         for i, t in enumerate(self.plan.tensors):
             buf, ld = e.act[t]

@@ -476,9 +476,9 @@ class DetectSession(object):
             if wh != largest:
                 e.add_size(g)
         if len(traced) > 1:
-            # the filters are folded with their BN statistics once, for the layers the binding current at that time does not fuse with a
+            # the filters are folded with their BN statistics once, for the layers a binding's plan does not fuse with a
             # pool: every size must fuse the same layers (true of sizes that are multiples of the network's stride)
-            fused = set(tuple(sorted(t.name for t in bnd['fused_pool'])) for bnd in e._bindings.values())
+            fused = set(tuple(sorted(t.name for t in bnd['plan'].fused_pool)) for bnd in e._bindings.values())
             if len(fused) != 1:
                 raise ValueError('sizes: the network fuses different layers with their pools at these sizes')
         self.models = {wh: gm[1] for wh, gm in traced.items()}
