@@ -534,6 +534,20 @@ int yolo2_ftrl(float *w, const float *g, float *accum, float *linear, long n, fl
  * d = ema - w; d = d * one_minus_decay; ema = ema - d, each rounded once in f32 (no FMA), NaN / inf propagating.  One launch; any n >= 1 and any
  * 4-byte aligned pointers (16-byte accesses where both are 16-byte aligned at the same element); 0 <= one_minus_decay <= 1. */
 int yolo2_ema_update(float *ema, const float *w, long n, float one_minus_decay, void *stream);
+/* Gradient accumulation, the mean over the micro-batches and weight decay in one launch over the flat f32 arenas (csrc/grad_combine.hip).
+ *   YOLO2_GRAD_STORE  acc[i] = g[i]                       (the first micro-batch: acc never needs zeroing)
+ *   YOLO2_GRAD_ADD    acc[i] = acc[i] + g[i]
+ *   YOLO2_GRAD_FINAL  s = g[i]; if (acc) s = acc[i] + s; s = s * scale; for i inside a range and decay != 0: s = s + decay * w[i]; g[i] = s;
+ *                     for i inside a range and shrink != 1: w[i] = w[i] * shrink      (decoupled decay: w *= 1 - lr * wd ahead of the update)
+ * Every operation is rounded once in f32 (no FMA), NaN / inf propagating; tests/grad_combine_ref.py states the same in NumPy and the two agree bit for bit.
+ * ranges_device: n_ranges >= 0 sorted, disjoint half-open element ranges {b0,e0,b1,e1,...} inside [0, n) in DEVICE memory, any begins and ends (the caller
+ * checks the order: yolo_tf_amd.ops.grad_ranges); it and w are read only in FINAL with n_ranges > 0 and (decay != 0 or shrink != 1), and must not be NULL then.
+ * n >= 0 (0: nothing is launched); acc must not be NULL in STORE / ADD; any 4-byte aligned pointers (16-byte accesses where the arenas that are read are aligned
+ * alike).  A workgroup takes chunks of YOLO2_GRAD_COMBINE_CHUNK elements and finds a chunk's place in the table once. */
+enum { YOLO2_GRAD_STORE = 0, YOLO2_GRAD_ADD = 1, YOLO2_GRAD_FINAL = 2 };
+#define YOLO2_GRAD_COMBINE_CHUNK 4096
+int yolo2_grad_combine(float *g, float *acc, float *w, long n, int mode, float scale, float decay, float shrink,
+                       const long *ranges_device, int n_ranges, void *stream);
 /* x *= scale (1/world averaging of the all-reduced gradient ahead of clip_by_norm) */
 int yolo2_scale(float *x, long n, float scale, void *stream);
 /* x[a:b] = 0 for nranges half-open element ranges given as a HOST array {a0,b0,a1,b1,...}: the accumulating filter

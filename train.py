@@ -33,7 +33,9 @@ import torch
 from yolo_tf_amd import checkpoint, multiscale, tf_checkpoint, utils
 from yolo_tf_amd.utils import events
 from yolo_tf_amd.parallel import agree, init_distributed, sync_replicas
-from yolo_tf_amd.session import BOX_LOSSES, CLASS_LOSSES, TrainSession, box_loss_option, loss_options, loss_options_set
+from yolo_tf_amd.optim import LR_KEYS, LR_POLICIES, learning_rate_fn
+from yolo_tf_amd.session import (BOX_LOSSES, CLASS_LOSSES, WEIGHT_DECAY_MODES, TrainSession, box_loss_option, loss_options, loss_options_set, recipe_options,
+                                 refuse_recipe)
 from yolo_tf_amd.summary import HistogramSummaries, ImageSummaries
 from yolo_tf_amd.utils import data as udata
 
@@ -77,6 +79,15 @@ def make_args(argv=None):
     parser.add_argument('--no_rescore', dest='rescore', action='store_false', help='turns [mi355x] rescore off')
     parser.add_argument('--label_smoothing', default=None, type=float, help='overrides [mi355x] label_smoothing: epsilon of the ce / focal class target (0: off)')
     parser.add_argument('--focal_gamma', default=None, type=float, help='overrides [mi355x] focal_gamma: the focusing exponent of class_loss focal, 0 or >= 1 (default 2)')
+    parser.add_argument('--accum_steps', default=None, type=int, help="overrides [mi355x] accum_steps: micro-batches of -b images per optimizer update (Darknet's subdivisions; "
+                        '1: off).  -s keeps counting updates')
+    parser.add_argument('--weight_decay', default=None, type=float, help='overrides [mi355x] weight_decay: decay of the convolution and fully connected filters (Darknet: 0.0005; 0: off)')
+    parser.add_argument('--weight_decay_mode', default=None, choices=list(WEIGHT_DECAY_MODES), help='overrides [mi355x] weight_decay_mode: l2 (wd * w joins the gradient; the '
+                        'default) or decoupled (AdamW: the filters are scaled by 1 - lr * wd ahead of the update)')
+    parser.add_argument('--lr_policy', default=None, choices=list(LR_POLICIES), help='overrides [mi355x] lr_policy: the learning-rate schedule (default: [exponential_decay] when present, else constant)')
+    parser.add_argument('--burn_in', default=None, type=int, help='overrides [mi355x] burn_in: the rate is multiplied by min(1, (step + 1) / N) ** burn_in_power over the first N updates (0: off)')
+    parser.add_argument('--lr_steps', default=None, nargs='+', help='overrides [mi355x] lr_steps: the updates at which lr_policy steps multiplies the rate by the matching entry of lr_scales')
+    parser.add_argument('--lr_scales', default=None, nargs='+', help='overrides [mi355x] lr_scales')
     parser.add_argument('--ckpt_format', default='npz', choices=['npz', 'tf'], help="checkpoint container: 'npz' (every optimizer) or 'tf' (TensorFlow V2 bundle, as the reference's tf.train.Saver writes)")
     return parser.parse_args(argv)
 
@@ -188,6 +199,28 @@ def loss_setting(args, config):
     return options
 
 
+def recipe_setting(args, config):
+    """[mi355x] accum_steps, weight_decay, weight_decay_mode and the learning-rate schedule's keys with the command line's overrides (written into ``config``,
+    where the session and optim.learning_rate_fn read them; -s stands in for an absent lr_max_steps): (accum_steps, weight_decay, weight_decay_mode).
+    Raises ValueError / NotImplementedError naming the key for an invalid value or a combination the session refuses, before anything is built."""
+    if not config.has_section('mi355x'):
+        config.add_section('mi355x')
+    for key in ('accum_steps', 'weight_decay', 'weight_decay_mode', 'lr_policy', 'burn_in'):
+        if getattr(args, key) is not None:
+            config.set('mi355x', key, str(getattr(args, key)))
+    for key in ('lr_steps', 'lr_scales'):
+        if getattr(args, key) is not None:
+            config.set('mi355x', key, ' '.join(getattr(args, key)))
+    policy = config.get('mi355x', 'lr_policy').strip().lower() if config.has_option('mi355x', 'lr_policy') else None
+    if policy in ('poly', 'cosine') and not config.has_option('mi355x', 'lr_max_steps') and args.steps is not None:
+        config.set('mi355x', 'lr_max_steps', str(args.steps))
+    learning_rate_fn(config, args.learning_rate)          # (called for its refusals only: the session builds its own)
+    recipe = recipe_options(config)
+    shard = config.getboolean('mi355x', 'shard_optimizer') if config.has_option('mi355x', 'shard_optimizer') else False
+    refuse_recipe(*recipe, v1=config.get('config', 'model') == 'yolo', shard_optimizer=shard, optimizer=args.optimizer)
+    return recipe
+
+
 def describe_loss_options(options):
     """One line for the log: the options of DESIGN.md section 22 that are on, or None."""
     on = loss_options_set(options)
@@ -203,6 +236,7 @@ def main():
     setting = multiscale_setting(args, config)       # (a refusal comes before the process group and the device are touched)
     composing = compose_setting(args, config)
     options = loss_setting(args, config)
+    accum_steps, weight_decay, weight_decay_mode = recipe_setting(args, config)
     rank, local_rank, world = init_distributed()
     torch.cuda.set_device(local_rank)
     model = config.get('config', 'model')
@@ -249,6 +283,10 @@ def main():
         logging.warning(describe_loss_options(session.loss_options))
     logging.warning('optimizer=%s, dtype=%s, world=%d, parameters=%d%s' % (args.optimizer, dtype, world, session.engine.n_params,
                                                                           ', ema_decay=%g' % session.ema_decay if session.ema is not None else ''))
+    if accum_steps > 1 or weight_decay > 0:
+        logging.warning('accum_steps=%d: effective batch %d (batch %d x accum_steps %d x world %d)%s' % (
+            accum_steps, args.batch_size * accum_steps * world, args.batch_size, accum_steps, world,
+            ', weight_decay=%g (%s)' % (weight_decay, weight_decay_mode) if weight_decay > 0 else ''))
     # rank 0 alone chooses and reads the checkpoint; the others receive parameters, statistics, optimizer slots and
     # global_step from it (same seed -> same initial weights anyway, but a restore must not depend on what each rank sees)
     # Both containers may sit in one logdir (a run resumed with the other --ckpt_format, or a logdir the reference wrote): the one
@@ -309,11 +347,16 @@ def main():
     n_rate = 0
     sync_every = 1 if world == 1 else 20     # data parallel: decisions only one rank can make are agreed on every 20 steps
     device = session.engine.device
+    scheduled = any(config.has_option('mi355x', key) for key in LR_KEYS)      # a schedule of DESIGN.md section 23: every update's rate at level info
     while args.steps is None or session.global_step < args.steps:
         multiscale.follow(session, schedule)         # (no schedule: nothing; otherwise the size of this step, logged when it changes)
         images, labels = data.next()
+        if scheduled and session.micro_step == 0:
+            logging.info('update %d: learning_rate=%r' % (session.global_step, session.lr_fn(session.global_step)))
         session.step(images, labels)
         n_rate += 1
+        if session.micro_step != 0:
+            continue                 # inside an update (accum_steps > 1): nothing is summarised, agreed on or saved until its last micro-batch has run
         last = args.steps is not None and session.global_step >= args.steps
         if not (last or session.global_step % sync_every == 0):
             continue

@@ -111,6 +111,7 @@ SIGNATURES = {
     'yolo2_ftrl': [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _p],
     'yolo2_scale': [_p, _l, _f, _p],
     'yolo2_ema_update': [_p, _p, _l, _f, _p],
+    'yolo2_grad_combine': [_p, _p, _p, _l, _i, _f, _f, _f, _p, _i, _p],
     'yolo2_zero_ranges': [_p, _p, _i, _p],
     'yolo2_bn_fold': [_p, _p, _p, _p, _p, _p, _p, _l, _i, _f, _p],
     'yolo2_selftest_tr16': [_p, _p],

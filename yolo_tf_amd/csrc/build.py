@@ -42,6 +42,7 @@ SOURCES = {
     'quant.hip': ['-ffp-contract=off'],
     'calib.hip': ['-ffp-contract=off'],
     'ema.hip': ['-ffp-contract=off'],
+    'grad_combine.hip': ['-ffp-contract=off'],
 }
 COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics', '-Wno-unused-result']
 LIB = os.path.join(HERE, 'libyolo2hip.so')

@@ -456,6 +456,37 @@ def ema_update(ema, w, n, one_minus_decay):
     call('yolo2_ema_update', ptr(ema), ptr(w), n, one_minus_decay, _stream())
 
 
+GRAD_STORE, GRAD_ADD, GRAD_FINAL = 0, 1, 2           # YOLO2_GRAD_*: mode of yolo2_grad_combine
+GRAD_COMBINE_CHUNK = 4096                            # YOLO2_GRAD_COMBINE_CHUNK: elements of one workgroup's chunk
+
+
+def check_grad_ranges(ranges, n):
+    """``ranges`` as a list of (begin, end) ints after checking what yolo2_grad_combine relies on: 0 <= begin < end <= n, sorted, disjoint
+    (adjacent ranges are fine).  Raises ValueError otherwise.  Pure host logic."""
+    out, last = [], 0
+    for b, e in ranges:
+        b, e = int(b), int(e)
+        if not (0 <= b < e <= n):
+            raise ValueError('grad_combine: the range [%d, %d) is empty or outside [0, %d)' % (b, e, n))
+        if b < last:
+            raise ValueError('grad_combine: the range [%d, %d) is out of order or overlaps the range before it (which ends at %d)' % (b, e, last))
+        out.append((b, e))
+        last = e
+    return out
+
+
+def grad_ranges(ranges, n, device):
+    """The device table of yolo2_grad_combine for ``ranges`` (checked by ``check_grad_ranges``): int64 [2 * len(ranges)], or None when there is none."""
+    flat = [v for be in check_grad_ranges(ranges, n) for v in be]
+    return torch.tensor(flat, dtype=torch.int64, device=device) if flat else None
+
+
+def grad_combine(g, acc, w, n, mode, scale=1.0, decay=0.0, shrink=1.0, table=None):
+    """One launch over ``n`` f32 elements (include/yolo2_hip.h yolo2_grad_combine): GRAD_STORE acc = g; GRAD_ADD acc += g; GRAD_FINAL
+    g = (acc + g) * scale (+ decay * w inside the table's ranges), w *= shrink inside them.  ``table``: what ``grad_ranges`` returned."""
+    call('yolo2_grad_combine', ptr(g), ptr(acc), ptr(w), n, mode, scale, decay, shrink, ptr(table), 0 if table is None else table.numel() // 2, _stream())
+
+
 def zero_ranges(x, ranges):
     """x[a:b] = 0 for every (a, b) in ``ranges`` (element offsets; host list)."""
     flat = (ctypes.c_long * (2 * len(ranges)))(*[int(v) for ab in ranges for v in ab])

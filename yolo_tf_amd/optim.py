@@ -10,7 +10,95 @@ import torch
 from . import ops
 
 
+LR_POLICIES = ('exponential', 'constant', 'steps', 'poly', 'cosine')
+LR_KEYS = ('lr_policy', 'lr_steps', 'lr_scales', 'lr_max_steps', 'lr_power', 'lr_min_ratio', 'burn_in', 'burn_in_power')
+
+
+def _numbers(config, key, convert):
+    """The values of ``[mi355x] key``, separated by spaces or commas, none of them negative."""
+    raw = config.get('mi355x', key)
+    try:
+        values = [convert(v) for v in raw.replace(',', ' ').split()]
+    except ValueError:
+        raise ValueError('[mi355x] %s = %r: not a list of numbers' % (key, raw))
+    if any(v < 0 for v in values):
+        raise ValueError('[mi355x] %s = %r: negative' % (key, raw))
+    return values
+
+
 def learning_rate_fn(config, base_lr):
+    """The learning rate of the update whose 0-based count (``global_step``) is ``step``, in Python floats.
+
+    With none of the ``[mi355x]`` schedule keys (LR_KEYS) present: lr * decay_rate ** floor(step / decay_steps) when [exponential_decay] is present, else
+    constant (reference train.py:116-124), the function as it was before the keys existed.  Otherwise:
+
+    ``lr_policy`` = exponential | constant | steps | poly | cosine (absent: [exponential_decay] when present, else constant)
+      steps   base * prod(lr_scales[i] for lr_steps[i] <= step)                                  (Darknet's policy = steps, steps, scales)
+      poly    base * (1 - s / max) ** lr_power                                                    (lr_power defaults to 4)
+      cosine  base * (lr_min_ratio + (1 - lr_min_ratio) * (1 + cos(pi * s / max)) / 2)            (lr_min_ratio defaults to 0)
+      with s = min(step, max) and max = ``lr_max_steps`` (train.py writes its -s there when the key is absent).
+    ``burn_in`` = N, ``burn_in_power`` (default 4, Darknet's): the policy's value times min(1, (step + 1) / N) ** power -- step + 1, so that the first
+    update is not a zero update.  ValueError names the key for an unknown policy, lr_steps and lr_scales of different lengths, poly or cosine without a
+    max, and negative values.  Pure host logic."""
+    has = lambda key: config is not None and hasattr(config, 'has_option') and config.has_option('mi355x', key)
+    if not any(has(key) for key in LR_KEYS):
+        return _reference_learning_rate_fn(config, base_lr)
+    policy = config.get('mi355x', 'lr_policy').strip().lower() if has('lr_policy') else None
+    if policy is not None and policy not in LR_POLICIES:
+        raise ValueError('[mi355x] lr_policy = %r: one of %s' % (config.get('mi355x', 'lr_policy'), ', '.join(LR_POLICIES)))
+    for key in ('lr_steps', 'lr_scales'):
+        if has(key) and policy != 'steps':
+            raise ValueError('[mi355x] %s belongs to lr_policy = steps, not %s' % (key, policy or 'the default policy'))
+
+    def one(key, convert, default):
+        if not has(key):
+            return default
+        values = _numbers(config, key, convert)
+        if len(values) != 1:
+            raise ValueError('[mi355x] %s = %r: one number' % (key, config.get('mi355x', key)))
+        return values[0]
+    if policy is None:
+        fn = _reference_learning_rate_fn(config, base_lr)
+    elif policy == 'exponential':
+        if not config.has_section('exponential_decay'):
+            raise ValueError('[mi355x] lr_policy = exponential: the config has no [exponential_decay] section')
+        fn = _reference_learning_rate_fn(config, base_lr)
+    elif policy == 'constant':
+        fn = lambda step: base_lr
+    elif policy == 'steps':
+        at = _numbers(config, 'lr_steps', int) if has('lr_steps') else []
+        scales = _numbers(config, 'lr_scales', float) if has('lr_scales') else []
+        if len(at) != len(scales):
+            raise ValueError('[mi355x] lr_steps has %d entries and lr_scales %d: one scale per step' % (len(at), len(scales)))
+        if sorted(at) != at:
+            raise ValueError('[mi355x] lr_steps = %r: not ascending' % config.get('mi355x', 'lr_steps'))
+
+        def fn(step):
+            lr = base_lr
+            for a, s in zip(at, scales):
+                if a <= step:
+                    lr *= s
+            return lr
+    else:
+        top = one('lr_max_steps', int, 0)
+        if top <= 0:
+            raise ValueError('[mi355x] lr_policy = %s needs a positive lr_max_steps (or train.py -s)' % policy)
+        if policy == 'poly':
+            power = one('lr_power', float, 4.0)
+            fn = lambda step: base_lr * (1.0 - min(step, top) / top) ** power
+        else:
+            floor = one('lr_min_ratio', float, 0.0)
+            if floor > 1.0:
+                raise ValueError('[mi355x] lr_min_ratio = %r: lies in [0, 1]' % floor)
+            fn = lambda step: base_lr * (floor + (1.0 - floor) * 0.5 * (1.0 + math.cos(math.pi * min(step, top) / top)))
+    burn = one('burn_in', int, 0)
+    burn_power = one('burn_in_power', float, 4.0)
+    if burn <= 0:
+        return fn
+    return lambda step: fn(step) * min(1.0, (step + 1) / burn) ** burn_power
+
+
+def _reference_learning_rate_fn(config, base_lr):
     """lr * decay_rate ** floor(step / decay_steps) when [exponential_decay] is present, else constant
     (reference train.py:116-124)."""
     try:

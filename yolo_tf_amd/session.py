@@ -94,6 +94,57 @@ def loss_options_set(options):
     return [k for k in ('class_loss', 'ignore_thresh', 'rescore', 'label_smoothing') if options[k] != LOSS_OPTION_DEFAULTS[k]]
 
 
+WEIGHT_DECAY_MODES = ('l2', 'decoupled')
+
+
+def recipe_options(config, accum_steps=None, weight_decay=None, weight_decay_mode=None):
+    """``accum_steps``, ``weight_decay`` and ``weight_decay_mode`` of a TrainSession as (int, float, str): each argument, or the
+    ``[mi355x]`` key of the same name where the argument is None; absent = (1, 0.0, 'l2'), which is off.  A value out of range raises ValueError naming
+    the key.  Pure host logic."""
+    def key(name, given, default):
+        if given is not None:
+            return given
+        return config.get('mi355x', name) if config is not None and config.has_option('mi355x', name) else default
+    k = key('accum_steps', accum_steps, 1)
+    try:
+        steps = int(str(k).strip())
+    except ValueError:
+        steps = 0
+    if steps < 1:
+        raise ValueError('accum_steps = %r: the micro-batches of one update, an integer >= 1 (1 or absent: off)' % (k,))
+    d = key('weight_decay', weight_decay, 0.0)
+    try:
+        decay = float(d)
+    except (TypeError, ValueError):
+        decay = -1.0
+    if not 0.0 <= decay < float('inf'):
+        raise ValueError('weight_decay = %r: a number >= 0 (0 or absent: off)' % (d,))
+    mode = str(key('weight_decay_mode', weight_decay_mode, 'l2')).strip().lower()
+    if mode not in WEIGHT_DECAY_MODES:
+        raise ValueError('weight_decay_mode = %r: one of %s (absent: l2)' % (mode, ', '.join(WEIGHT_DECAY_MODES)))
+    return steps, decay, mode
+
+
+def refuse_recipe(accum_steps, weight_decay, weight_decay_mode, v1, shard_optimizer, optimizer):
+    """What gradient accumulation and weight decay do not cover, each refusal naming its key; called before anything touches the device."""
+    if accum_steps > 1 and v1:
+        raise NotImplementedError('accum_steps = %d covers the YOLOv2 family: the dropout masks of YOLO (v1) are drawn per global_step, every micro-batch of '
+                                  'an update would get the same one' % accum_steps)
+    on = ['accum_steps = %d' % accum_steps] * (accum_steps > 1) + ['weight_decay = %g' % weight_decay] * (weight_decay > 0)
+    if on and shard_optimizer:
+        raise NotImplementedError('[mi355x] shard_optimizer with %s: the sharded update runs inside the bucket chains during backward, before the '
+                                  'accumulated gradient exists; turn one of them off' % on[0])
+    if weight_decay > 0 and weight_decay_mode == 'decoupled' and optimizer == 'ftrl':
+        raise NotImplementedError('weight_decay_mode = decoupled with the ftrl optimizer: FTRL recomputes a weight from its accumulators, a shrunk weight '
+                                  'would be overwritten; use weight_decay_mode = l2 (or [optimizer_ftrl] l2_regularization_strength)')
+
+
+def decay_ranges(param_offsets):
+    """The element ranges of the parameter arena that weight decay covers: the variables named .../weights (convolution and fully connected filters; gamma,
+    beta and biases are not decayed -- Darknet's choice), sorted by offset.  Pure host logic."""
+    return sorted((o, o + n) for name, (o, n) in param_offsets.items() if name.rsplit('/', 1)[-1] == 'weights')
+
+
 def ema_decay_at(ema_decay, t):
     """[TF-sem] tf.train.ExponentialMovingAverage(decay, num_updates=t): min(decay, (1 + t) / (10 + t)), in Python floats."""
     return min(ema_decay, (1.0 + t) / (10.0 + t))
@@ -107,7 +158,8 @@ class TrainSession(object):
     def __init__(self, builder, batch_size, dtype='bf16', optimizer='adam', learning_rate=1e-6, gradient_clip=0.0,
                  config=None, seed=0, world_size=1, bucket_mb=64.0, preprocess_mode=0, sizes=None, grad_dtype='f32', comm_cus=None, comm_timing=False,
                  sync_bn=False, shard_optimizer=False, deterministic=None, ema_decay=None, box_loss=None,
-                 class_loss=None, ignore_thresh=None, rescore=None, label_smoothing=None, focal_gamma=None):
+                 class_loss=None, ignore_thresh=None, rescore=None, label_smoothing=None, focal_gamma=None,
+                 accum_steps=None, weight_decay=None, weight_decay_mode=None):
         """``sizes``: optional list of (width, height) input sizes for multi-scale training (BASELINE configs[3]); buffers are
         allocated once for the largest, ``set_size`` switches between them, the builder's configured size is selected first.
 
@@ -123,8 +175,20 @@ class TrainSession(object):
         'diou', 'ciou'.  None (default): ``[mi355x] box_loss`` of the config; absent or 'mse': the loss call made before the option existed.
 
         ``class_loss`` ('mse' | 'ce' | 'focal'), ``ignore_thresh``, ``rescore``, ``label_smoothing``, ``focal_gamma``: the other options of the
-        YOLOv2 loss.  None (default): the ``[mi355x]`` key of the same name; absent: off, the loss call as it was."""
+        YOLOv2 loss.  None (default): the ``[mi355x]`` key of the same name; absent: off, the loss call as it was.
+
+        ``accum_steps`` = K: gradient accumulation (Darknet's subdivisions).  ``step()`` is then one MICRO-batch: K - 1 of them run forward,
+        loss and backward and add their gradient into a second arena, the K-th forms the mean and updates; ``micro_step`` counts 0 .. K - 1, ``global_step``
+        counts updates.  ``weight_decay`` with ``weight_decay_mode`` 'l2' (wd * w joins the gradient of the filters before the collective, the clip and the
+        optimizer) or 'decoupled' (AdamW: the filters are scaled by 1 - lr * wd ahead of the update).  None (default): the ``[mi355x]`` key of the same
+        name; absent, 1 and 0: off -- nothing is allocated, no launch is added."""
         assert builder.training, 'call builder(data, training=True) first'
+        self.accum_steps, self.weight_decay, self.weight_decay_mode = recipe_options(config if config is not None else getattr(builder, 'config', None),
+                                                                                      accum_steps, weight_decay, weight_decay_mode)
+        refuse_recipe(self.accum_steps, self.weight_decay, self.weight_decay_mode, getattr(builder, 'family', 'yolo2') == 'yolo', shard_optimizer, optimizer)
+        self._recipe = self.accum_steps > 1 or self.weight_decay > 0          # False: step() is the step it was before the options existed
+        self.micro_step = 0
+        self._update_due = False             # True between the last micro-batch's forward_backward() and its apply_gradients()
         self.ema_decay = ema_decay_option(ema_decay, config if config is not None else getattr(builder, 'config', None))
         self.loss_options = loss_options(config if config is not None else getattr(builder, 'config', None), box_loss, class_loss, ignore_thresh,
                                          rescore, label_smoothing, focal_gamma)
@@ -216,7 +280,7 @@ class TrainSession(object):
         # layer, tests/test_network_gpu.py).  Measured SLOWER: 3.72 vs 3.62 ms per step (profiles/r05_early_adam.txt) -- the update's thousands
         # of small workgroups (16.6 KB of LDS each) occupy CUs that the 150 KB convolution workgroups then cannot be placed on.
         self.early_adam = (os.environ.get('YOLO2_EARLY_ADAM', '0') == '1' and not self.deterministic and world_size == 1 and optimizer == 'adam' and self.fuse_adam_prep
-                           and self.gradient_clip <= 0 and not getattr(e, '_has_l2', False) and dev.type == 'cuda')
+                           and self.gradient_clip <= 0 and not getattr(e, '_has_l2', False) and dev.type == 'cuda' and not self._recipe)
         self.opt_stream = torch.cuda.Stream(device=dev) if self.early_adam else None
         self._early_pending = False
         self._in_step = False            # the early-update candidate only runs inside step(): forward_backward() + apply_gradients() as one unit
@@ -231,6 +295,10 @@ class TrainSession(object):
             self.ema = staggered(e.n_params, torch.float32, dev)
             self.ema.copy_(e.params)
             self.ema_var = {name: self.ema[o:o + n] for name, (o, n) in e.param_offsets.items()}
+        # gradient accumulation: the running sum of the micro-gradients, an arena laid out like engine.grads (never zeroed: the first micro-batch stores);
+        # weight decay: the device table of the filters' ranges (csrc/grad_combine.hip), built once
+        self.grad_acc = staggered(e.n_params, torch.float32, dev) if self.accum_steps > 1 else None
+        self.decay_table = ops.grad_ranges(decay_ranges(e.param_offsets), e.n_params, dev) if self.weight_decay > 0 else None
 
     def set_size(self, width, height):
         """Input size of the following steps (one of the sizes the session was built with); weights, statistics, optimizer state
@@ -247,7 +315,8 @@ class TrainSession(object):
 
     def forward_backward(self, images, defer_collectives=False):
         """Gradients are final (all-reduced) on return unless ``defer_collectives``: then the buckets may still be on the wire
-        and ``apply_gradients`` consumes them one by one (what ``step`` does)."""
+        and ``apply_gradients`` consumes them one by one (what ``step`` does).  With ``accum_steps`` > 1 this is micro-batch ``micro_step``: all but the last
+        of an update leave their gradient in ``grad_acc`` and advance ``micro_step``; ``apply_gradients`` follows the last one only (``_backward_recipe``)."""
         e, m = self.engine, self.model
         assert not self._early_pending, 'a layer-wise early update is half applied: apply_gradients() must follow the forward_backward() of step()'
         e.dropout_step = self.global_step
@@ -266,7 +335,9 @@ class TrainSession(object):
             ops.loss_partials(logits, ld, self.anchors, self.labels, self.hparam, dlogits, self.loss_ws, self.B, m.cell_height, m.cell_width, self.A, self.C,
                               **self.loss_options)
             self._objectives_pending = (m.cell_height, m.cell_width)
-        if self.reducer is not None:
+        if self._recipe:
+            self._backward_recipe(defer_collectives)
+        elif self.reducer is not None:
             self.reducer.begin()
             # optimizer sharding only inside step(): a bare forward_backward() promises complete (all-reduced) gradients and no update
             self.reducer.shard = self.shard_optimizer and defer_collectives
@@ -299,8 +370,39 @@ class TrainSession(object):
         else:
             e.backward()
 
+    def _backward_recipe(self, defer_collectives):
+        """Backward of micro-batch ``micro_step`` with gradient accumulation and / or weight decay on.  Micro-batches 0 .. K - 2 are
+        local: backward, then one launch that stores (the first) or adds the gradient into ``grad_acc`` -- no collective, clip, optimizer or EMA, no
+        change of ``global_step``.  The last one: backward without per-layer hooks, then ONE launch that leaves (sum of the micro-gradients) * f32(1 / K), plus
+        wd * w over the filters in l2 mode, in ``engine.grads`` (decoupled mode scales the filters by f32(1 - lr * wd) there instead), and only then the
+        collective, every bucket at once: the L2 term must be in before a bucket leaves, so this all-reduce is not overlapped with backward."""
+        e, K = self.engine, self.accum_steps
+        e.backward()
+        self._update_due = self.micro_step == K - 1
+        if not self._update_due:
+            ops.grad_combine(e.grads, self.grad_acc, None, e.n_params, ops.GRAD_STORE if self.micro_step == 0 else ops.GRAD_ADD)
+            self.micro_step += 1
+            return
+        decay, shrink = 0.0, 1.0
+        if self.weight_decay > 0 and self.weight_decay_mode == 'l2':
+            decay = self.weight_decay
+        elif self.weight_decay > 0:
+            shrink = float(np.float32(1.0 - self.lr_fn(self.global_step) * self.weight_decay))
+            e._filters_dirty = True          # the masters changed under the prepared layouts (the fused Adam launch rewrites them, every other update path marks them too)
+        ops.grad_combine(e.grads, self.grad_acc, e.params, e.n_params, ops.GRAD_FINAL, float(np.float32(1.0 / K)), decay, shrink, self.decay_table)
+        if self.reducer is not None:
+            self.reducer.begin()
+            self.reducer.shard = False
+            self._sharded_pending = False
+            self._deferred = defer_collectives and self.gradient_clip <= 0 and self.bucketed_update
+            self.reducer.finish(wait=not self._deferred)
+
     def apply_gradients(self):
         e = self.engine
+        if self._recipe:
+            assert self._update_due, 'micro-batch %d of %d: the update follows the last micro-batch' % (self.micro_step, self.accum_steps)
+            self._update_due = False
+            self.micro_step = 0
         if self.gradient_clip > 0:
             # [TF-sem] clip happens on the (averaged) gradient: scale first when data-parallel
             if self.world_size > 1:
@@ -369,6 +471,8 @@ class TrainSession(object):
         self.optimizer_state_complete = True
 
     def step(self, images, labels=None):
+        """One training step; with ``accum_steps`` = K > 1 one MICRO-batch: ``global_step`` (and with it the learning rate, the EMA and every checkpoint)
+        moves on every K-th call, when ``micro_step`` is back at 0."""
         # a failure the device reported during an EARLIER step (completed snapshot): a single process raises here, at most eight steps late instead of one
         # summary interval; data-parallel callers read async_error_pending() / device_error() and agree on it first (train.py) -- a rank
         # that raised alone would leave its peers waiting in the next collective
@@ -379,6 +483,8 @@ class TrainSession(object):
         self._in_step = True
         try:
             self.forward_backward(images, defer_collectives=True)
+            if self._recipe and not self._update_due:
+                return               # micro-batch 0 .. K - 2 of an update: accumulated, nothing else changes
             self.apply_gradients()
         finally:
             self._in_step = False
@@ -400,7 +506,8 @@ class TrainSession(object):
 
     def fetch(self):
         """Synchronises and returns {'total_loss', 'iou_best', 'iou_normal', 'coords', 'prob'} of the last step
-        (the five scalars the reference summarises, config.ini:63)."""
+        (the five scalars the reference summarises, config.ini:63).  With ``accum_steps`` > 1 these are the objectives of the last MICRO-batch that ran,
+        not a mean over the update's micro-batches."""
         if getattr(self, '_objectives_pending', None):
             ops.loss_objectives(self.loss_ws, self.objectives_dev, self.B, self._objectives_pending[0], self._objectives_pending[1], self.A)
             self._objectives_pending = None
