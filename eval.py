@@ -21,7 +21,7 @@ import json
 import logging
 import os
 
-from yolo_tf_amd import utils
+from yolo_tf_amd import options, utils
 
 PREPROCESS = {'std': 0, 'darknet': 1}
 
@@ -52,7 +52,7 @@ def main():
     utils.ensure_names(config)
     builder = yolo.Builder(args, config)
     builder(None)
-    dtype = args.dtype or (config.get('mi355x', 'dtype') if config.has_option('mi355x', 'dtype') else 'bf16')
+    dtype = options.read(config, 'dtype', args.dtype or None)
     args.nms, args.sigma = utils.nms_options(args, config)      # --nms / --sigma, else [mi355x] nms / nms_sigma, else hard
     logdir = utils.get_logdir(config)
     calibration = None
@@ -186,14 +186,7 @@ def make_args(argv=None):
     parser.add_argument('--sizes', default=None, help="evaluate the one checkpoint at several input sizes: entries S, WxH or LO-HI (squares in steps of the "
                         "network's stride) separated by spaces or commas, e.g. '320-608'; prints one table per size and a closing one, --json gets by_size")
     parser.add_argument('--ema', action='store_true', help='use the moving averages of the weights a run with [mi355x] ema_decay keeps in its checkpoints')
-    parser.add_argument('--nms', default=None, choices=list(utils.NMS_METHODS),
-                        help="suppression: 'hard' (the reference's NMS; the default) or Soft-NMS with 'linear' or 'gaussian' decay; default [mi355x] nms")
-    parser.add_argument('--sigma', type=float, default=None, help='--nms gaussian: the decay is exp(-IoU^2 / sigma), at least 1/64 (default [mi355x] nms_sigma, else 0.5)')
-    parser.add_argument('--tta', default=None, help="test-time augmentation: 'flip' and / or sizes (S, WxH, LO-HI) separated by spaces or commas, e.g. "
-                        "'flip 320 608'; every batch runs at each view and the boxes are fused on the device (Weighted Boxes Fusion) into one result; "
-                        "default [mi355x] tta; not with --sizes")
-    parser.add_argument('--tta_iou', type=float, default=None, help='--tta: a box joins a fused box at this IoU or above (default [mi355x] tta_iou, else 0.55, '
-                        "the paper's default; not tuned here)")
+    options.add_flags(parser, ('nms', ('sigma', 'nms_sigma'), 'tta', 'tta_iou'))         # None: the key, or its default, decides
     parser.add_argument('--level', default='info', help='logging level')
     return parser.parse_args(argv)
 

@@ -23,11 +23,12 @@ sys.path.insert(0, ROOT)
 
 def step_time(args):
     from bench import make_builder
+    from yolo_tf_amd import options
     from yolo_tf_amd.session import TrainSession
     from yolo_tf_amd.utils import data
     builder, cfg = make_builder('darknet', args.names, args.size, True, tempfile.mkdtemp(prefix='box_loss_bench_'))
     kw = dict(box_loss=args.box_loss) if args.box_loss != 'mse' else {}       # (absent: the parent's constructor call, so a baseline library's session builds too)
-    sess = TrainSession(builder, args.batch, dtype=args.dtype, optimizer='adam', learning_rate=1e-6, seed=0, bucket_mb=cfg.getfloat('mi355x', 'bucket_mb'), **kw)
+    sess = TrainSession(builder, args.batch, dtype=args.dtype, optimizer='adam', learning_rate=1e-6, seed=0, bucket_mb=options.read(cfg, 'bucket_mb'), **kw)
     cells = args.size // 32
     images = torch.rand(args.batch, args.size, args.size, 3, device='cuda', generator=torch.Generator(device='cuda').manual_seed(1234)) * 255.0
     sess.upload_labels(data.synthetic_batch(args.batch, args.names, cells, cells, seed=4321))

@@ -33,11 +33,12 @@ CONFIGS = {
 
 def step_time(args):
     from bench import make_builder
+    from yolo_tf_amd import options
     from yolo_tf_amd.session import TrainSession
     from yolo_tf_amd.utils import data
     builder, cfg = make_builder('darknet', args.names, args.size, True, tempfile.mkdtemp(prefix='loss_opt_bench_'))
     kw = CONFIGS[args.options]          # (off: the parent's constructor call, so a baseline library's session builds too)
-    sess = TrainSession(builder, args.batch, dtype=args.dtype, optimizer='adam', learning_rate=1e-6, seed=0, bucket_mb=cfg.getfloat('mi355x', 'bucket_mb'), **kw)
+    sess = TrainSession(builder, args.batch, dtype=args.dtype, optimizer='adam', learning_rate=1e-6, seed=0, bucket_mb=options.read(cfg, 'bucket_mb'), **kw)
     cells = args.size // 32
     images = torch.rand(args.batch, args.size, args.size, 3, device='cuda', generator=torch.Generator(device='cuda').manual_seed(1234)) * 255.0
     sess.upload_labels(data.synthetic_batch(args.batch, args.names, cells, cells, seed=4321))

@@ -27,7 +27,7 @@ B, W, H, CLASSES = 16, 416, 416, 20
 def kernels(args):
     import numpy as np
     import torch
-    from yolo_tf_amd import ops
+    from yolo_tf_amd import ops, options
     from yolo_tf_amd.utils import augment as A
     rng = np.random.RandomState(0)
     images = [rng.randint(0, 256, (375, 500, 3)).astype(np.uint8) for _ in range(64)]
@@ -36,14 +36,11 @@ def kernels(args):
         k = rng.randint(1, 7)
         x0, y0 = rng.uniform(0, 250, k), rng.uniform(0, 180, k)
         objects.append((rng.randint(0, CLASSES, k), np.stack([x0, y0, x0 + rng.uniform(20, 240, k), y0 + rng.uniform(20, 180, k)], 1)))
-    ini = configparser.ConfigParser()
-    ini.read(os.path.join(ROOT, 'config.ini'))
 
     def pipeline(**keys):
-        for k in ('mosaic', 'mixup'):
-            ini.remove_option('mi355x', k)
-        for k, v in keys.items():
-            ini.set('mi355x', k, str(v))
+        ini = configparser.ConfigParser()          # (a fresh one: the shipped file sets neither mosaic nor mixup)
+        ini.read(os.path.join(ROOT, 'config.ini'))
+        options.write(ini, argparse.Namespace(**keys), keys)
         cfg = A.AugmentConfig(ini)
         cfg.full_probability = cfg.probability = 1.0          # every branch taken: worst case
         cfg.grayscale_probability = 0.0
@@ -141,11 +138,12 @@ def step(args, mosaic):
     import torch
     import train
     from bench import make_builder
+    from yolo_tf_amd import options
     from yolo_tf_amd.session import TrainSession
     with tempfile.TemporaryDirectory() as basedir:
         builder, cfg = make_builder('darknet', CLASSES, W, True, basedir)
         if mosaic:
-            cfg.set('mi355x', 'mosaic', '1')
+            options.write(cfg, argparse.Namespace(mosaic=1), ['mosaic'])
         sess = TrainSession(builder, B, dtype='bf16', optimizer='adam', learning_rate=1e-6, seed=0)
         data = train.DeviceAugmentedData(np.load(args.dataset, allow_pickle=True), B, W, H, CLASSES, W // 32, H // 32, cfg, 0, 0, 1, sess)
         assert data.pipe.cfg.compose == bool(mosaic)

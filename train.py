@@ -30,12 +30,11 @@ import time
 import numpy as np
 import torch
 
-from yolo_tf_amd import checkpoint, multiscale, tf_checkpoint, utils
+from yolo_tf_amd import checkpoint, multiscale, options, tf_checkpoint, utils
 from yolo_tf_amd.utils import events
 from yolo_tf_amd.parallel import agree, init_distributed, sync_replicas
-from yolo_tf_amd.optim import LR_KEYS, LR_POLICIES, learning_rate_fn
-from yolo_tf_amd.session import (BOX_LOSSES, CLASS_LOSSES, WEIGHT_DECAY_MODES, TrainSession, box_loss_option, loss_options, loss_options_set, recipe_options,
-                                 refuse_recipe)
+from yolo_tf_amd.optim import LR_KEYS, learning_rate_fn
+from yolo_tf_amd.session import TrainSession, box_loss_option, loss_options, loss_options_set, recipe_options, refuse_recipe
 from yolo_tf_amd.summary import HistogramSummaries, ImageSummaries
 from yolo_tf_amd.utils import data as udata
 
@@ -64,30 +63,10 @@ def make_args(argv=None):
     parser.add_argument('--dtype', default=None, choices=['bf16', 'f32'], help='overrides [mi355x] dtype')
     parser.add_argument('--deterministic', action='store_true', help='bitwise reproducible training steps (also [mi355x] deterministic / YOLO2_DETERMINISTIC=1): '
                         'filter gradients summed through a workspace in a fixed order, no float atomics anywhere in the step')
-    parser.add_argument('--multiscale', default=None, help="overrides [mi355x] multiscale: input sizes drawn during training, entries S, WxH or LO-HI (squares in "
-                        "steps of the network's stride) separated by spaces or commas, e.g. '320-608'; '' turns it off")
-    parser.add_argument('--multiscale_every', default=None, type=int, help='overrides [mi355x] multiscale_every: steps a drawn size holds (default 10)')
-    parser.add_argument('--mosaic', default=None, type=float, help='overrides [mi355x] mosaic: probability that a training image is a 2x2 mosaic of four dataset images (0: off)')
-    parser.add_argument('--mixup', default=None, type=float, help='overrides [mi355x] mixup: probability that a training image is blended with a second one, MixUp (0: off)')
-    parser.add_argument('--box_loss', default=None, choices=list(BOX_LOSSES), help='overrides [mi355x] box_loss: the box regression term of the YOLOv2 loss, mse (the '
-                        "reference's squared error; the default) or 1 - IoU / GIoU / DIoU / CIoU of the responsible anchor's box")
-    parser.add_argument('--class_loss', default=None, choices=list(CLASS_LOSSES), help="overrides [mi355x] class_loss: the class term of the YOLOv2 loss, mse (the reference's "
-                        'squared error on the softmax; the default), ce (cross-entropy) or focal')
-    parser.add_argument('--ignore_thresh', default=None, type=float, help='overrides [mi355x] ignore_thresh: a lane that is not responsible and predicts a ground truth box '
-                        'with an IoU above this is left out of the no-object term (Darknet: 0.6; 0: off)')
     parser.add_argument('--rescore', default=None, action='store_true', help="[mi355x] rescore: the responsible anchor's objectness target is its IoU instead of 1")
     parser.add_argument('--no_rescore', dest='rescore', action='store_false', help='turns [mi355x] rescore off')
-    parser.add_argument('--label_smoothing', default=None, type=float, help='overrides [mi355x] label_smoothing: epsilon of the ce / focal class target (0: off)')
-    parser.add_argument('--focal_gamma', default=None, type=float, help='overrides [mi355x] focal_gamma: the focusing exponent of class_loss focal, 0 or >= 1 (default 2)')
-    parser.add_argument('--accum_steps', default=None, type=int, help="overrides [mi355x] accum_steps: micro-batches of -b images per optimizer update (Darknet's subdivisions; "
-                        '1: off).  -s keeps counting updates')
-    parser.add_argument('--weight_decay', default=None, type=float, help='overrides [mi355x] weight_decay: decay of the convolution and fully connected filters (Darknet: 0.0005; 0: off)')
-    parser.add_argument('--weight_decay_mode', default=None, choices=list(WEIGHT_DECAY_MODES), help='overrides [mi355x] weight_decay_mode: l2 (wd * w joins the gradient; the '
-                        'default) or decoupled (AdamW: the filters are scaled by 1 - lr * wd ahead of the update)')
-    parser.add_argument('--lr_policy', default=None, choices=list(LR_POLICIES), help='overrides [mi355x] lr_policy: the learning-rate schedule (default: [exponential_decay] when present, else constant)')
-    parser.add_argument('--burn_in', default=None, type=int, help='overrides [mi355x] burn_in: the rate is multiplied by min(1, (step + 1) / N) ** burn_in_power over the first N updates (0: off)')
-    parser.add_argument('--lr_steps', default=None, nargs='+', help='overrides [mi355x] lr_steps: the updates at which lr_policy steps multiplies the rate by the matching entry of lr_scales')
-    parser.add_argument('--lr_scales', default=None, nargs='+', help='overrides [mi355x] lr_scales')
+    options.add_flags(parser, ('multiscale', 'multiscale_every', 'mosaic', 'mixup', 'box_loss', 'class_loss', 'ignore_thresh', 'label_smoothing', 'focal_gamma', 'accum_steps',
+                               'weight_decay', 'weight_decay_mode', 'lr_policy', 'burn_in', 'lr_steps', 'lr_scales'))
     parser.add_argument('--ckpt_format', default='npz', choices=['npz', 'tf'], help="checkpoint container: 'npz' (every optimizer) or 'tf' (TensorFlow V2 bundle, as the reference's tf.train.Saver writes)")
     return parser.parse_args(argv)
 
@@ -163,19 +142,15 @@ def compose_setting(args, config):
     them): None when both are off (nothing about the run changes), otherwise the options of utils.augment.compose_options.  Raises ValueError for
     an invalid key and for data without raw objects, before anything is built."""
     from yolo_tf_amd.utils.augment import compose_options
-    for key in ('mosaic', 'mixup'):
-        if getattr(args, key) is not None:
-            if not config.has_section('mi355x'):
-                config.add_section('mi355x')
-            config.set('mi355x', key, repr(getattr(args, key)))
-    options = compose_options(config)
-    if not (options['mosaic'] > 0 or options['mixup'] > 0):
+    options.write(config, args, ('mosaic', 'mixup'))
+    composing = compose_options(config)
+    if not (composing['mosaic'] > 0 or composing['mixup'] > 0):
         return None
     if args.data == 'synthetic' or (args.data != 'cache' and 'objects_coord' not in np.load(args.data, allow_pickle=True).files):
         raise ValueError('[mi355x] mosaic = %g, mixup = %g: --data %s holds no raw objects; mosaic and MixUp compose training images from decoded '
                          'images and their boxes (objects_class, objects_coord, objects_first in a .npz, or the dataset cache)'
-                         % (options['mosaic'], options['mixup'], args.data))
-    return options
+                         % (composing['mosaic'], composing['mixup'], args.data))
+    return composing
 
 
 def box_loss_setting(args, config):
@@ -191,51 +166,42 @@ def box_loss_setting(args, config):
 def loss_setting(args, config):
     """Every loss option ([mi355x] box_loss, class_loss, ignore_thresh, rescore, label_smoothing, focal_gamma) with the command line's overrides, as
     session.loss_options returns them.  Raises ValueError for an invalid value and for the YOLO (v1) family with any option on, before anything is built."""
-    box_loss_setting(args, config)       # (called for its refusals only: unknown mode, YOLO (v1) with another mode than mse; loss_options resolves the value again)
-    options = loss_options(config, args.box_loss, args.class_loss, args.ignore_thresh, args.rescore, args.label_smoothing, args.focal_gamma)
-    on = loss_options_set(options)
+    box_loss = box_loss_setting(args, config)       # (first: its refusals come before those of the other options)
+    resolved = loss_options(config, box_loss, args.class_loss, args.ignore_thresh, args.rescore, args.label_smoothing, args.focal_gamma)
+    on = loss_options_set(resolved)
     if on and config.get('config', 'model') == 'yolo':
-        raise ValueError('[mi355x] %s = %s: the loss options cover the YOLOv2 family; the YOLO (v1) loss has its own objectness and class terms only' % (on[0], options[on[0]]))
-    return options
+        raise ValueError('[mi355x] %s = %s: the loss options cover the YOLOv2 family; the YOLO (v1) loss has its own objectness and class terms only' % (on[0], resolved[on[0]]))
+    return resolved
 
 
 def recipe_setting(args, config):
     """[mi355x] accum_steps, weight_decay, weight_decay_mode and the learning-rate schedule's keys with the command line's overrides (written into ``config``,
     where the session and optim.learning_rate_fn read them; -s stands in for an absent lr_max_steps): (accum_steps, weight_decay, weight_decay_mode).
     Raises ValueError / NotImplementedError naming the key for an invalid value or a combination the session refuses, before anything is built."""
-    if not config.has_section('mi355x'):
-        config.add_section('mi355x')
-    for key in ('accum_steps', 'weight_decay', 'weight_decay_mode', 'lr_policy', 'burn_in'):
-        if getattr(args, key) is not None:
-            config.set('mi355x', key, str(getattr(args, key)))
-    for key in ('lr_steps', 'lr_scales'):
-        if getattr(args, key) is not None:
-            config.set('mi355x', key, ' '.join(getattr(args, key)))
-    policy = config.get('mi355x', 'lr_policy').strip().lower() if config.has_option('mi355x', 'lr_policy') else None
-    if policy in ('poly', 'cosine') and not config.has_option('mi355x', 'lr_max_steps') and args.steps is not None:
-        config.set('mi355x', 'lr_max_steps', str(args.steps))
-    learning_rate_fn(config, args.learning_rate)          # (called for its refusals only: the session builds its own)
+    options.write(config, args, ('accum_steps', 'weight_decay', 'weight_decay_mode', 'lr_policy', 'burn_in', 'lr_steps', 'lr_scales'))
+    if (options.read(config, 'lr_policy') or '').strip().lower() in ('poly', 'cosine') and not options.has(config, 'lr_max_steps'):
+        options.write(config, argparse.Namespace(lr_max_steps=args.steps), ('lr_max_steps',))
+    learning_rate_fn(config, args.learning_rate)          # (for its refusals: the schedule has no value to hand on, the session makes its function of the same config)
     recipe = recipe_options(config)
-    shard = config.getboolean('mi355x', 'shard_optimizer') if config.has_option('mi355x', 'shard_optimizer') else False
-    refuse_recipe(*recipe, v1=config.get('config', 'model') == 'yolo', shard_optimizer=shard, optimizer=args.optimizer)
+    refuse_recipe(*recipe, v1=config.get('config', 'model') == 'yolo', shard_optimizer=options.read(config, 'shard_optimizer'), optimizer=args.optimizer)
     return recipe
 
 
-def describe_loss_options(options):
+def describe_loss_options(resolved):
     """One line for the log: the options of DESIGN.md section 22 that are on, or None."""
-    on = loss_options_set(options)
+    on = loss_options_set(resolved)
     if not on:
         return None
-    parts = ['%s=%s' % (k, options[k]) for k in on]
-    if options['class_loss'] == 'focal':
-        parts.append('focal_gamma=%g' % options['focal_gamma'])
+    parts = ['%s=%s' % (k, resolved[k]) for k in on]
+    if resolved['class_loss'] == 'focal':
+        parts.append('focal_gamma=%g' % resolved['focal_gamma'])
     return 'loss options: ' + ', '.join(parts)
 
 
 def main():
     setting = multiscale_setting(args, config)       # (a refusal comes before the process group and the device are touched)
     composing = compose_setting(args, config)
-    options = loss_setting(args, config)
+    loss = loss_setting(args, config)
     accum_steps, weight_decay, weight_decay_mode = recipe_setting(args, config)
     rank, local_rank, world = init_distributed()
     torch.cuda.set_device(local_rank)
@@ -255,7 +221,7 @@ def main():
     builder = yolo.Builder(args, config)
     builder(None, training=True)
     builder.create_objectives()
-    dtype = args.dtype or (config.get('mi355x', 'dtype') if config.has_option('mi355x', 'dtype') else 'bf16')
+    dtype = options.read(config, 'dtype', args.dtype or None)
     seed = args.seed if args.seed is not None else 0
     sizes, schedule, downsampling = None, None, None
     if setting is not None:
@@ -270,12 +236,10 @@ def main():
             composing['mosaic'], composing['mosaic_scale'][0], composing['mosaic_scale'][1], composing['mosaic_fill'], composing['mixup'], composing['mixup_alpha']))
     session = TrainSession(builder, args.batch_size, dtype=dtype, optimizer=args.optimizer, learning_rate=args.learning_rate,
                            gradient_clip=args.gradient_clip, config=config, seed=seed, world_size=world, sizes=sizes,
-                           bucket_mb=config.getfloat('mi355x', 'bucket_mb') if config.has_option('mi355x', 'bucket_mb') else 64.0,
-                           grad_dtype=config.get('mi355x', 'grad_dtype') if config.has_option('mi355x', 'grad_dtype') else 'f32',
-                           sync_bn=config.getboolean('mi355x', 'sync_bn') if config.has_option('mi355x', 'sync_bn') else False,
-                           shard_optimizer=config.getboolean('mi355x', 'shard_optimizer') if config.has_option('mi355x', 'shard_optimizer') else False,
+                           **{key: options.read(config, key) for key in ('bucket_mb', 'grad_dtype', 'sync_bn', 'shard_optimizer')},
                            deterministic=True if args.deterministic else None,      # (None: [mi355x] deterministic / YOLO2_DETERMINISTIC decide)
-                           **options)       # (always given: --box_loss mse must win over a config key; all off is the call made before the options existed)
+                           accum_steps=accum_steps, weight_decay=weight_decay, weight_decay_mode=weight_decay_mode,
+                           **loss)          # (always given: --box_loss mse must win over a config key; all off is the call made before the options existed)
     if session.box_loss != 'mse':
         logging.warning('box_loss: %s (1 - %s of the responsible box, weighted by [yolo2_hparam] coords = %g)' % (
             session.box_loss, {'iou': 'IoU', 'giou': 'GIoU', 'diou': 'DIoU', 'ciou': 'CIoU'}[session.box_loss], builder.hparam['coords']))
@@ -347,7 +311,7 @@ def main():
     n_rate = 0
     sync_every = 1 if world == 1 else 20     # data parallel: decisions only one rank can make are agreed on every 20 steps
     device = session.engine.device
-    scheduled = any(config.has_option('mi355x', key) for key in LR_KEYS)      # a schedule of DESIGN.md section 23: every update's rate at level info
+    scheduled = any(options.has(config, key) for key in LR_KEYS)      # a schedule of DESIGN.md section 23: every update's rate at level info
     while args.steps is None or session.global_step < args.steps:
         multiscale.follow(session, schedule)         # (no schedule: nothing; otherwise the size of this step, logged when it changes)
         images, labels = data.next()

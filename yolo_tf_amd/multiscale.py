@@ -10,8 +10,10 @@ import re
 
 import numpy as np
 
+from . import options
+
 KEY, KEY_EVERY = 'multiscale', 'multiscale_every'
-DEFAULT_EVERY = 10              # the paper's value
+DEFAULT_EVERY = options.KEYS[KEY_EVERY].default              # 10, the paper's value
 
 
 def parse_sizes(spec, dw, dh):
@@ -72,16 +74,13 @@ def configure(config, spec=None, every=None):
     (sizes, every, added): the sorted size list, which always holds the configured width x height (``added`` says whether it had to be put
     in).  Raises ValueError naming the key and the reason: the YOLO (v1) family, a bad entry, a list no member of which contains the rest."""
     from . import utils
-    has = lambda key: config.has_section('mi355x') and config.has_option('mi355x', key)
-    if spec is None:
-        spec = config.get('mi355x', KEY) if has(KEY) else ''
+    spec = options.read(config, KEY, spec)
     if not spec.strip():
         return None
     model = config.get('config', 'model')
     if model == 'yolo':
         raise ValueError('[mi355x] %s = %r: the fully connected head of the YOLO (v1) family fixes the input size' % (KEY, spec))
-    if every is None:
-        every = config.getint('mi355x', KEY_EVERY) if has(KEY_EVERY) else DEFAULT_EVERY
+    every = options.read(config, KEY_EVERY, every)
     if int(every) < 1:
         raise ValueError('[mi355x] %s = %d: a size holds for at least one step' % (KEY_EVERY, every))
     dw, dh = utils.get_downsampling(config)

@@ -6,7 +6,7 @@ import os
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, options
 from .engine import Engine, layer_end_offsets, staggered
 from .graph import pad8
 from .model.yolo2 import OBJECTIVE_KEYS
@@ -21,105 +21,90 @@ def _label_shapes(B, cells, C):
 def ema_decay_option(ema_decay, config):
     """The ``ema_decay`` of a TrainSession as a float: the argument, or ``[mi355x] ema_decay`` of the config when the argument is None; absent or 0 = off
     (returned as 0.0).  Anything outside [0, 1) raises ValueError.  Pure host logic."""
-    if ema_decay is None:
-        ema_decay = config.getfloat('mi355x', 'ema_decay') if config is not None and config.has_option('mi355x', 'ema_decay') else 0.0
+    ema_decay = options.read(config, 'ema_decay', ema_decay)
     decay = float(ema_decay)
     if not 0.0 <= decay < 1.0:
         raise ValueError('ema_decay = %r: the decay of the weight average lies in [0, 1) (0 or absent: off)' % (ema_decay,))
     return decay
 
 
-BOX_LOSSES = ('mse', 'iou', 'giou', 'diou', 'ciou')
+BOX_LOSSES = options.KEYS['box_loss'].choices
 
 
 def box_loss_option(box_loss, config):
     """The ``box_loss`` of a TrainSession: the argument, or ``[mi355x] box_loss`` of the config when the argument is None; absent = 'mse'.
     Anything but mse, iou, giou, diou, ciou raises ValueError.  Pure host logic."""
-    if box_loss is None:
-        box_loss = config.get('mi355x', 'box_loss') if config is not None and config.has_option('mi355x', 'box_loss') else 'mse'
+    box_loss = options.read(config, 'box_loss', box_loss)
     name = str(box_loss).strip().lower()
     if name not in BOX_LOSSES:
         raise ValueError('box_loss = %r: the box regression loss is one of %s (absent: mse)' % (box_loss, ', '.join(BOX_LOSSES)))
     return name
 
 
-CLASS_LOSSES = ('mse', 'ce', 'focal')
-LOSS_OPTION_DEFAULTS = {'box_loss': 'mse', 'class_loss': 'mse', 'ignore_thresh': 0.0, 'rescore': False, 'label_smoothing': 0.0, 'focal_gamma': 2.0}
+CLASS_LOSSES = options.KEYS['class_loss'].choices
+LOSS_OPTION_DEFAULTS = {k: options.KEYS[k].default for k in ('box_loss', 'class_loss', 'ignore_thresh', 'rescore', 'label_smoothing', 'focal_gamma')}
 
 
 def loss_options(config, box_loss=None, class_loss=None, ignore_thresh=None, rescore=None, label_smoothing=None, focal_gamma=None):
     """Every option of the YOLOv2 loss of a TrainSession (DESIGN.md sections 21, 22) as the keyword arguments of ``ops.loss``: each argument, or
     the ``[mi355x]`` key of the same name where the argument is None; absent = off (LOSS_OPTION_DEFAULTS).  An unknown name or a value out of
     range raises ValueError naming the option.  Pure host logic."""
-    def key(name, given, read):
-        if given is not None:
-            return given
-        if config is not None and config.has_option('mi355x', name):
-            try:
-                return read('mi355x', name)
-            except ValueError:
-                raise ValueError('[mi355x] %s = %r: not a valid value' % (name, config.get('mi355x', name)))
-        return LOSS_OPTION_DEFAULTS[name]
-
-    def number(name, v):
+    def number(name, given):
+        v = options.read(config, name, given, invalid='not a valid value')
         try:
             return float(v)
         except (TypeError, ValueError):
             raise ValueError('%s = %r: a number' % (name, v))
     out = {'box_loss': box_loss_option(box_loss, config)}
-    cls = key('class_loss', class_loss, config.get if config is not None else None)
+    cls = options.read(config, 'class_loss', class_loss)
     out['class_loss'] = str(cls).strip().lower()
     if out['class_loss'] not in CLASS_LOSSES:
         raise ValueError('class_loss = %r: the class term is one of %s (absent: mse)' % (cls, ', '.join(CLASS_LOSSES)))
-    t = number('ignore_thresh', key('ignore_thresh', ignore_thresh, config.getfloat if config is not None else None))
+    t = number('ignore_thresh', ignore_thresh)
     if not (t == 0.0 or 0.0 < t < 1.0):
         raise ValueError('ignore_thresh = %r: the ignore threshold lies inside (0, 1) (0 or absent: off)' % (t,))
-    r = key('rescore', rescore, config.getboolean if config is not None else None)
+    r = options.read(config, 'rescore', rescore, invalid='not a valid value')
     if r not in (False, True, 0, 1):
         raise ValueError('rescore = %r: true or false' % (r,))
-    eps = number('label_smoothing', key('label_smoothing', label_smoothing, config.getfloat if config is not None else None))
+    eps = number('label_smoothing', label_smoothing)
     if not 0.0 <= eps < 1.0:
         raise ValueError('label_smoothing = %r: lies in [0, 1) (0 or absent: off)' % (eps,))
     if eps != 0.0 and out['class_loss'] == 'mse':
         raise ValueError('label_smoothing = %r with class_loss = mse: smoothing belongs to the ce and focal class terms' % (eps,))
-    gamma = number('focal_gamma', key('focal_gamma', focal_gamma, config.getfloat if config is not None else None))
+    gamma = number('focal_gamma', focal_gamma)
     if out['class_loss'] == 'focal' and not (gamma == 0.0 or 1.0 <= gamma < float('inf')):       # (read with focal only, as ops.loss_options and the library do)
         raise ValueError('focal_gamma = %r: 0 or at least 1 (absent: 2)' % (gamma,))
     out.update(ignore_thresh=t, rescore=bool(r), label_smoothing=eps, focal_gamma=gamma)
     return out
 
 
-def loss_options_set(options):
+def loss_options_set(resolved):
     """The names of the options of ``loss_options`` that are on, box_loss aside (focal_gamma counts only with the focal class term)."""
-    return [k for k in ('class_loss', 'ignore_thresh', 'rescore', 'label_smoothing') if options[k] != LOSS_OPTION_DEFAULTS[k]]
+    return [k for k in ('class_loss', 'ignore_thresh', 'rescore', 'label_smoothing') if resolved[k] != LOSS_OPTION_DEFAULTS[k]]
 
 
-WEIGHT_DECAY_MODES = ('l2', 'decoupled')
+WEIGHT_DECAY_MODES = options.KEYS['weight_decay_mode'].choices
 
 
 def recipe_options(config, accum_steps=None, weight_decay=None, weight_decay_mode=None):
     """``accum_steps``, ``weight_decay`` and ``weight_decay_mode`` of a TrainSession as (int, float, str): each argument, or the
     ``[mi355x]`` key of the same name where the argument is None; absent = (1, 0.0, 'l2'), which is off.  A value out of range raises ValueError naming
     the key.  Pure host logic."""
-    def key(name, given, default):
-        if given is not None:
-            return given
-        return config.get('mi355x', name) if config is not None and config.has_option('mi355x', name) else default
-    k = key('accum_steps', accum_steps, 1)
+    k = options.read(config, 'accum_steps', accum_steps, how='text')           # (the texts: the refusals quote them)
     try:
         steps = int(str(k).strip())
     except ValueError:
         steps = 0
     if steps < 1:
         raise ValueError('accum_steps = %r: the micro-batches of one update, an integer >= 1 (1 or absent: off)' % (k,))
-    d = key('weight_decay', weight_decay, 0.0)
+    d = options.read(config, 'weight_decay', weight_decay, how='text')
     try:
         decay = float(d)
     except (TypeError, ValueError):
         decay = -1.0
     if not 0.0 <= decay < float('inf'):
         raise ValueError('weight_decay = %r: a number >= 0 (0 or absent: off)' % (d,))
-    mode = str(key('weight_decay_mode', weight_decay_mode, 'l2')).strip().lower()
+    mode = str(options.read(config, 'weight_decay_mode', weight_decay_mode)).strip().lower()
     if mode not in WEIGHT_DECAY_MODES:
         raise ValueError('weight_decay_mode = %r: one of %s (absent: l2)' % (mode, ', '.join(WEIGHT_DECAY_MODES)))
     return steps, decay, mode
@@ -183,15 +168,14 @@ class TrainSession(object):
         optimizer) or 'decoupled' (AdamW: the filters are scaled by 1 - lr * wd ahead of the update).  None (default): the ``[mi355x]`` key of the same
         name; absent, 1 and 0: off -- nothing is allocated, no launch is added."""
         assert builder.training, 'call builder(data, training=True) first'
-        self.accum_steps, self.weight_decay, self.weight_decay_mode = recipe_options(config if config is not None else getattr(builder, 'config', None),
-                                                                                      accum_steps, weight_decay, weight_decay_mode)
+        cfg = config if config is not None else getattr(builder, 'config', None)         # the one config every option below is read from
+        self.accum_steps, self.weight_decay, self.weight_decay_mode = recipe_options(cfg, accum_steps, weight_decay, weight_decay_mode)
         refuse_recipe(self.accum_steps, self.weight_decay, self.weight_decay_mode, getattr(builder, 'family', 'yolo2') == 'yolo', shard_optimizer, optimizer)
         self._recipe = self.accum_steps > 1 or self.weight_decay > 0          # False: step() is the step it was before the options existed
         self.micro_step = 0
         self._update_due = False             # True between the last micro-batch's forward_backward() and its apply_gradients()
-        self.ema_decay = ema_decay_option(ema_decay, config if config is not None else getattr(builder, 'config', None))
-        self.loss_options = loss_options(config if config is not None else getattr(builder, 'config', None), box_loss, class_loss, ignore_thresh,
-                                         rescore, label_smoothing, focal_gamma)
+        self.ema_decay = ema_decay_option(ema_decay, cfg)
+        self.loss_options = loss_options(cfg, box_loss, class_loss, ignore_thresh, rescore, label_smoothing, focal_gamma)
         self.box_loss = self.loss_options['box_loss']
         self.builder = builder
         self.B = batch_size
@@ -211,9 +195,7 @@ class TrainSession(object):
         largest = max(traced, key=lambda wh: wh[0] * wh[1])
         assert all(w <= largest[0] and h <= largest[1] for w, h in traced), 'one size must contain all the others'
         if deterministic is None:
-            cfg = config if config is not None else getattr(builder, 'config', None)
-            deterministic = (cfg is not None and cfg.has_option('mi355x', 'deterministic') and cfg.getboolean('mi355x', 'deterministic')) or \
-                os.environ.get('YOLO2_DETERMINISTIC', '0') == '1'
+            deterministic = options.read(cfg, 'deterministic') or os.environ.get('YOLO2_DETERMINISTIC', '0') == '1'
         self.deterministic = bool(deterministic)
         if self.deterministic and self.v1:
             raise NotImplementedError('deterministic=True covers the YOLOv2 family: the YOLO (v1) loss and fully connected head still sum in arrival order')
@@ -244,8 +226,8 @@ class TrainSession(object):
         self.size = None
         self.set_size(*own)
         self.hparam = [builder.hparam[k] for k in OBJECTIVE_KEYS]
-        self.optimizer = Optimizer(optimizer, config if config is not None else builder.config, e.n_params, dev)
-        self.lr_fn = learning_rate_fn(config if config is not None else builder.config, learning_rate)
+        self.optimizer = Optimizer(optimizer, cfg, e.n_params, dev)
+        self.lr_fn = learning_rate_fn(cfg, learning_rate)
         self.gradient_clip = float(gradient_clip)
         self.clip_ws = torch.zeros(ops.workspace_bytes('clip_fixed' if self.deterministic else 'clip', e.n_seg) // 8, dtype=torch.float64, device=dev)
         self.global_step = 0
@@ -266,8 +248,7 @@ class TrainSession(object):
         if world_size > 1:
             # the collectives' persistent kernels hold CUs for their whole duration: stream-K launches (one workgroup per CU) are sized
             # for what is left ([mi355x] comm_cus, default 32 -- an RCCL ring's channel count on this part)
-            cfg = config if config is not None else builder.config
-            reserve = comm_cus if comm_cus is not None else (cfg.getint('mi355x', 'comm_cus') if cfg is not None and cfg.has_option('mi355x', 'comm_cus') else 32)
+            reserve = options.read(cfg, 'comm_cus', comm_cus)
             total = torch.cuda.get_device_properties(dev).multi_processor_count
             ops.set_stream_workgroups(max(64, total - int(reserve)) if reserve > 0 else 0)
         if world_size > 1 and torch.distributed.is_available() and torch.distributed.is_initialized():

@@ -7,9 +7,10 @@ the frame of the fused result.  ``parse_views`` reads the spec of ``--tta`` / ``
 import re
 
 from . import multiscale
+from .options import KEYS as OPTION_KEYS, read as read_option
 
 KEY, KEY_IOU = 'tta', 'tta_iou'
-DEFAULT_IOU = 0.55             # the paper's default; not tuned here
+DEFAULT_IOU = OPTION_KEYS[KEY_IOU].default             # 0.55, the paper's default; not tuned here
 M_LIMIT = 32768                # yolo2_wbf: pooled boxes per image
 
 
@@ -81,12 +82,7 @@ def describe(views):
 
 def options(config, spec=None, iou=None):
     """(spec, fuse_iou): ``[mi355x] tta`` / ``tta_iou`` of ``config``, overridden by the arguments (the command line's) that are not None."""
-    has = lambda key: config.has_section('mi355x') and config.has_option('mi355x', key)
-    if spec is None:
-        spec = config.get('mi355x', KEY) if has(KEY) else ''
-    if iou is None:
-        iou = config.getfloat('mi355x', KEY_IOU) if has(KEY_IOU) else DEFAULT_IOU
-    iou = float(iou)
+    spec, iou = read_option(config, KEY, spec), float(read_option(config, KEY_IOU, iou))
     if not (iou == iou and abs(iou) != float('inf')):
         raise ValueError('[mi355x] %s = %r: the fusion overlap must be finite' % (KEY_IOU, iou))
     return spec, iou

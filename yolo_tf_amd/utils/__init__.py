@@ -4,6 +4,8 @@ import os
 
 import numpy as np
 
+from .. import options
+
 
 def _expand(path):
     return os.path.expanduser(os.path.expandvars(path))
@@ -66,15 +68,13 @@ def ensure_names(config):
     return dst
 
 
-NMS_METHODS = ('hard', 'linear', 'gaussian')
+NMS_METHODS = options.KEYS['nms'].choices
 
 
 def nms_options(args, config):
     """(method, sigma) of detect.py / eval.py: --nms / --sigma, else [mi355x] nms / nms_sigma, else ('hard', 0.5)."""
-    method = getattr(args, 'nms', None) or (config.get('mi355x', 'nms') if config.has_option('mi355x', 'nms') else 'hard')
-    sigma = getattr(args, 'sigma', None)
-    if sigma is None:
-        sigma = config.getfloat('mi355x', 'nms_sigma') if config.has_option('mi355x', 'nms_sigma') else 0.5
+    method = options.read(config, 'nms', getattr(args, 'nms', None) or None)           # (an empty --nms is none)
+    sigma = options.read(config, 'nms_sigma', getattr(args, 'sigma', None))
     if method not in NMS_METHODS:
         raise ValueError('[mi355x] nms must be one of %s, not %r' % (', '.join(NMS_METHODS), method))
     return method, float(sigma)

@@ -21,7 +21,7 @@ import ctypes
 import numpy as np
 import torch
 
-from .. import ops
+from .. import ops, options
 from .._lib import AugmentParams, ComposeTile
 
 FLIP, BRIGHTNESS, SATURATION, HUE, CONTRAST, NOISE, GRAY = 1, 2, 4, 8, 16, 32, 64
@@ -58,51 +58,32 @@ class AugmentConfig(object):
         return self.mosaic > 0 or self.mixup > 0
 
 
-COMPOSE_DEFAULTS = dict(mosaic=0.0, mosaic_scale=(0.5, 1.5), mosaic_center=0.25, mosaic_min_visible=0.25, mosaic_fill=114.0, mixup=0.0,
-                        mixup_alpha=1.5)
+COMPOSE_RULES = (          # key, what it must satisfy, what a refusal says -- in the order the keys are checked
+    ('mosaic', lambda p: 0.0 <= p <= 1.0, 'a probability per output image, in [0, 1] (0 or absent: off)'),
+    ('mixup', lambda p: 0.0 <= p <= 1.0, 'a probability per output image, in [0, 1] (0 or absent: off)'),
+    ('mosaic_scale', lambda lo, hi: 0.0 < lo <= hi, 'LO HI with 0 < LO <= HI, the range of a tile\'s size relative to the frame'),
+    ('mosaic_center', lambda c: 0.0 <= c <= 0.5, 'the centre is drawn from [c, 1 - c] of the frame: c lies in [0, 0.5]'),
+    ('mosaic_min_visible', lambda v: 0.0 <= v <= 1.0, 'the share of a box\'s area that must stay visible, in [0, 1]'),
+    ('mosaic_fill', lambda g: 0.0 <= g <= 255.0, 'a grey level in [0, 255]'),
+    ('mixup_alpha', lambda a: a > 0.0, 'the parameter of Beta(alpha, alpha) is positive'))
+COMPOSE_DEFAULTS = {key: options.KEYS[key].default for key in ('mosaic', 'mosaic_scale', 'mosaic_center', 'mosaic_min_visible', 'mosaic_fill', 'mixup', 'mixup_alpha')}
 
 
 def compose_options(config):
     """The mosaic / MixUp keys of ``[mi355x]`` as a dict of COMPOSE_DEFAULTS' keys; an absent key is its default, and ``mosaic`` / ``mixup``
     absent or 0 mean off.  An invalid value raises ValueError naming the key.  Pure host logic."""
     out = dict(COMPOSE_DEFAULTS)
-    if config is None or not config.has_section('mi355x'):
-        return out
-
-    def numbers(key, count):
-        text = config.get('mi355x', key)
-        try:
-            values = [float(v) for v in text.replace(',', ' ').split()]
-        except ValueError:
-            values = None
-        if values is None or len(values) != count or not all(np.isfinite(values)):
-            raise ValueError('[mi355x] %s = %r: expected %s' % (key, text, 'a number' if count == 1 else '%d numbers' % count))
-        return values
-
-    def check(key, ok, what):
-        if not ok:
-            raise ValueError('[mi355x] %s = %r: %s' % (key, config.get('mi355x', key), what))
-
-    for key in ('mosaic', 'mixup'):
-        if config.has_option('mi355x', key):
-            out[key], = numbers(key, 1)
-            check(key, 0.0 <= out[key] <= 1.0, 'a probability per output image, in [0, 1] (0 or absent: off)')
-    if config.has_option('mi355x', 'mosaic_scale'):
-        lo, hi = numbers('mosaic_scale', 2)
-        check('mosaic_scale', 0.0 < lo <= hi, 'LO HI with 0 < LO <= HI, the range of a tile\'s size relative to the frame')
-        out['mosaic_scale'] = (lo, hi)
-    if config.has_option('mi355x', 'mosaic_center'):
-        out['mosaic_center'], = numbers('mosaic_center', 1)
-        check('mosaic_center', 0.0 <= out['mosaic_center'] <= 0.5, 'the centre is drawn from [c, 1 - c] of the frame: c lies in [0, 0.5]')
-    if config.has_option('mi355x', 'mosaic_min_visible'):
-        out['mosaic_min_visible'], = numbers('mosaic_min_visible', 1)
-        check('mosaic_min_visible', 0.0 <= out['mosaic_min_visible'] <= 1.0, 'the share of a box\'s area that must stay visible, in [0, 1]')
-    if config.has_option('mi355x', 'mosaic_fill'):
-        out['mosaic_fill'], = numbers('mosaic_fill', 1)
-        check('mosaic_fill', 0.0 <= out['mosaic_fill'] <= 255.0, 'a grey level in [0, 255]')
-    if config.has_option('mi355x', 'mixup_alpha'):
-        out['mixup_alpha'], = numbers('mixup_alpha', 1)
-        check('mixup_alpha', out['mixup_alpha'] > 0.0, 'the parameter of Beta(alpha, alpha) is positive')
+    for key, ok, what in COMPOSE_RULES:
+        if not options.has(config, key):
+            continue
+        count = np.size(COMPOSE_DEFAULTS[key])          # as many numbers as the default holds
+        expected = 'expected ' + ('a number' if count == 1 else '%d numbers' % count)
+        values = options.read(config, key, how='list', invalid=expected)
+        if len(values) != count or not all(np.isfinite(values)):
+            raise options.refusal(config, key, expected)
+        if not ok(*values):
+            raise options.refusal(config, key, what)
+        out[key] = values[0] if count == 1 else tuple(values)
     return out
 
 
