@@ -433,6 +433,36 @@ int yolo2_loss_ex_partials(const void *logits, int ld, const float *anchors, con
                            const float *hparam, void *dlogits, float *ws, int B, int cell_h, int cell_w, int A, int C, int dtype,
                            void *stream, const yolo2_loss_options *opt);
 
+/* ---- objectness-scaled distillation (Mehta & Ozturk, ECCV-W 2018; csrc/distill.hip) -------------------
+ * Two YOLOv2 heads of the same geometry: `student` [B,cells,ld_s] (dtype_s) and `teacher` [B,cells,ld_t] (dtype_t), each YOLO2_F32 or
+ * YOLO2_BF16 and the two may differ; the real channels of a row are A x (iou, x, y, w, h, C classes).  With n = B*cells*A, s / t a
+ * lane of the student / teacher, sg the sigmoid and m = sg(t0) (scale_by_objectness 1) or 1 (0), the three UNWEIGHTED objectives are
+ *   objectness = 1/n sum (sg(s0) - sg(t0))^2
+ *   coords     = 1/n sum m [(sg(s1) - sg(t1))^2 + (sg(s2) - sg(t2))^2 + (s3 - t3)^2 + (s4 - t4)^2]
+ *   prob       = 1/n sum m sum_k (p_k - q_k)^2                       class_term 0 (mse), p = softmax(s[5:] / T), q = softmax(t[5:] / T)
+ *              = 1/n sum m T^2 sum_k q_k (log q_k - log p_k)         class_term 1 (kl)
+ * and total = weight * (w_objectness * objectness + w_coords * coords + w_prob * prob).  The teacher is a constant.
+ * yolo2_distill_partials ADDS d total / d student into dlogits (dtype_s, [B,cells,ld_s], read and written: dl = store(f32(dl) + g) over
+ * the A*(5+C) real channels of a row; padding channels are not touched; NULL: objectives only) and stores three partial sums per
+ * workgroup into ws (yolo2_distill_workspace_bytes) with plain stores; yolo2_distill_objectives reduces them in index order into
+ * objectives f32[3] {objectness, coords, prob}.  No atomics: bitwise reproducible.  A NULL student, teacher, ws or opt, an unknown dtype, a
+ * size other than sizeof(yolo2_distill_options), a temperature that is not positive and finite, a negative or non-finite weight and an
+ * unknown class_term are argument errors: nothing is launched, nothing is written. */
+typedef struct yolo2_distill_options {
+    int   size;                 /* sizeof(yolo2_distill_options) */
+    int   class_term;           /* 0 mse, 1 kl */
+    int   scale_by_objectness;  /* 0 | 1 */
+    float weight;               /* the global weight, >= 0 */
+    float w_objectness;         /* >= 0 */
+    float w_coords;             /* >= 0 */
+    float w_prob;               /* >= 0 */
+    float temperature;          /* T > 0 */
+} yolo2_distill_options;
+size_t yolo2_distill_workspace_bytes(int B, int cells, int A);
+int yolo2_distill_partials(const void *student, int ld_s, int dtype_s, const void *teacher, int ld_t, int dtype_t, void *dlogits,
+                           float *ws, int B, int cell_h, int cell_w, int A, int C, void *stream, const yolo2_distill_options *opt);
+int yolo2_distill_objectives(const float *ws, float *objectives, int B, int cell_h, int cell_w, int A, void *stream);
+
 /* ---- YOLO (v1) family, SURVEY 8f-4: model/yolo/__init__.py:37-100, model/yolo/inference.py:24-66 --------------------------
  * Network output row per image [cells*C class scores | cells*boxes*(iou, x, y, sqrt_w, sqrt_h)], all linear; `ld` = row stride.
  * yolo1_loss: Objectives + d(total weighted loss)/d(net) (label tensors and hparam order as yolo2_loss; prob is masked by the

@@ -18,7 +18,10 @@ reference's own TFRecord cache (<cachedir>/<profile>.tfrecord for every ``-p`` p
 ``--multiscale SPEC`` / ``[mi355x] multiscale`` trains at a size drawn from a list every ``--multiscale_every`` steps (yolo_tf_amd/multiscale.py).
 ``--box_loss MODE`` / ``[mi355x] box_loss`` regresses the responsible anchor's box with 1 - IoU / GIoU / DIoU / CIoU instead of the squared error (YOLOv2 family).
 ``--ignore_thresh T``, ``--rescore``, ``--class_loss mse|ce|focal``, ``--label_smoothing E``, ``--focal_gamma G`` (and the ``[mi355x]`` keys of the same names) are the other
-options of the YOLOv2 loss: Darknet's ignore threshold, the IoU objectness target, a cross-entropy or focal class term."""
+options of the YOLOv2 loss: Darknet's ignore threshold, the IoU objectness target, a cross-entropy or focal class term.
+``--teacher CFG [CFG ...]`` / ``[distill] teacher`` distils the network from a trained YOLOv2 teacher with the same anchors, classes and grid (DESIGN.md section 25;
+``--teacher_ckpt``, ``--teacher_ema``, ``--teacher_dtype``, ``--distill_weight`` ... are the section's other keys).  The teacher is not saved with the student: a
+resumed run names it again."""
 import argparse
 import configparser
 import logging
@@ -31,6 +34,7 @@ import numpy as np
 import torch
 
 from yolo_tf_amd import checkpoint, multiscale, options, tf_checkpoint, utils
+from yolo_tf_amd import distill as distillation
 from yolo_tf_amd.utils import events
 from yolo_tf_amd.parallel import agree, init_distributed, sync_replicas
 from yolo_tf_amd.optim import LR_KEYS, learning_rate_fn
@@ -67,6 +71,7 @@ def make_args(argv=None):
     parser.add_argument('--no_rescore', dest='rescore', action='store_false', help='turns [mi355x] rescore off')
     options.add_flags(parser, ('multiscale', 'multiscale_every', 'mosaic', 'mixup', 'box_loss', 'class_loss', 'ignore_thresh', 'label_smoothing', 'focal_gamma', 'accum_steps',
                                'weight_decay', 'weight_decay_mode', 'lr_policy', 'burn_in', 'lr_steps', 'lr_scales'))
+    distillation.add_flags(parser)
     parser.add_argument('--ckpt_format', default='npz', choices=['npz', 'tf'], help="checkpoint container: 'npz' (every optimizer) or 'tf' (TensorFlow V2 bundle, as the reference's tf.train.Saver writes)")
     return parser.parse_args(argv)
 
@@ -187,6 +192,54 @@ def recipe_setting(args, config):
     return recipe
 
 
+def distill_setting(args, config):
+    """The [distill] section with the command line's overrides (yolo_tf_amd/distill.py): None when no teacher is named or the weight is 0 (nothing about
+    the run changes), otherwise every key resolved.  Raises ValueError naming the key for an invalid value and for the YOLO (v1) family, before anything is built."""
+    resolved = distillation.options(config, **distillation.from_args(args))
+    if not distillation.enabled(resolved):
+        return None
+    if config.get('config', 'model') == 'yolo':
+        raise ValueError('[distill] teacher = %s: distillation covers the YOLOv2 family; the YOLO (v1) head has no anchors to pair with a teacher\'s'
+                         % ' '.join(resolved['teacher']))
+    return resolved
+
+
+def build_teacher(resolved, width, height, batch_size, sizes):
+    """The teacher of a distilling run: a DetectSession of the network the [distill] teacher config files describe, at the student's input size(s) and
+    batch, with the weights of [distill] teacher_ckpt or of the latest checkpoint in the teacher's logdir (the .npz container first, else a
+    TensorFlow prefix, as detect.py looks for them).  A teacher without a checkpoint is an error: an untrained teacher teaches noise."""
+    from yolo_tf_amd.session import DetectSession
+    tconfig = configparser.ConfigParser()
+    utils.load_config(tconfig, resolved['teacher'])
+    model = tconfig.get('config', 'model')
+    if model == 'yolo':
+        raise ValueError('[distill] teacher = %s: distillation covers the YOLOv2 family; the teacher is a YOLO (v1) network' % ' '.join(resolved['teacher']))
+    tconfig.set(model, 'width', str(width))          # the teacher reads the student's images
+    tconfig.set(model, 'height', str(height))
+    utils.ensure_names(tconfig)
+    builder = __import__('yolo_tf_amd.model.' + model, fromlist=['Builder']).Builder(None, tconfig)
+    builder(None)
+    teacher = DetectSession(builder, batch_size, dtype=resolved['teacher_dtype'], sizes=sizes)
+    logdir = utils.get_logdir(tconfig)
+    path = os.path.expanduser(os.path.expandvars(resolved['teacher_ckpt']))
+    if path:
+        if not (os.path.exists(path) or os.path.exists(path + '.index')):
+            raise FileNotFoundError('distillation needs a trained teacher: the teacher checkpoint %s does not exist' % path)
+        tf_prefix = os.path.exists(path + '.index')
+    else:
+        path = checkpoint.latest_checkpoint(logdir)
+        tf_prefix = path is None
+        if tf_prefix:
+            path = tf_checkpoint.latest_checkpoint(logdir)
+        if path is None:
+            raise FileNotFoundError('distillation needs a trained teacher: no teacher checkpoint in %s (train the teacher first, or name its checkpoint '
+                                    'with --teacher_ckpt / [distill] teacher_ckpt)' % logdir)
+    step = (tf_checkpoint if tf_prefix else checkpoint).restore(path, engine=teacher.engine, ema=resolved['teacher_ema'])
+    logging.warning('distillation: teacher %s (%s) from %s (global_step=%d%s)' % (
+        tconfig.get(model, 'inference'), resolved['teacher_dtype'], path, step, ', averaged weights' if resolved['teacher_ema'] else ''))
+    return teacher
+
+
 def describe_loss_options(resolved):
     """One line for the log: the options of DESIGN.md section 22 that are on, or None."""
     on = loss_options_set(resolved)
@@ -203,6 +256,7 @@ def main():
     composing = compose_setting(args, config)
     loss = loss_setting(args, config)
     accum_steps, weight_decay, weight_decay_mode = recipe_setting(args, config)
+    distilling = distill_setting(args, config)
     rank, local_rank, world = init_distributed()
     torch.cuda.set_device(local_rank)
     model = config.get('config', 'model')
@@ -234,12 +288,14 @@ def main():
     if composing is not None:
         logging.warning('mosaic: probability %g, scale %g-%g, fill %g; mixup: probability %g, alpha %g' % (
             composing['mosaic'], composing['mosaic_scale'][0], composing['mosaic_scale'][1], composing['mosaic_fill'], composing['mixup'], composing['mixup_alpha']))
+    # [distill]: every rank keeps a teacher of its own, restored from the same file; it is not part of the student's checkpoints, a resumed run names it again
+    teaching = dict(teacher=build_teacher(distilling, width, height, args.batch_size, sizes), distill=distillation.kernel_options(distilling)) if distilling else {}
     session = TrainSession(builder, args.batch_size, dtype=dtype, optimizer=args.optimizer, learning_rate=args.learning_rate,
                            gradient_clip=args.gradient_clip, config=config, seed=seed, world_size=world, sizes=sizes,
                            **{key: options.read(config, key) for key in ('bucket_mb', 'grad_dtype', 'sync_bn', 'shard_optimizer')},
                            deterministic=True if args.deterministic else None,      # (None: [mi355x] deterministic / YOLO2_DETERMINISTIC decide)
                            accum_steps=accum_steps, weight_decay=weight_decay, weight_decay_mode=weight_decay_mode,
-                           **loss)          # (always given: --box_loss mse must win over a config key; all off is the call made before the options existed)
+                           **teaching, **loss)          # (always given: --box_loss mse must win over a config key; all off is the call made before the options existed)
     if session.box_loss != 'mse':
         logging.warning('box_loss: %s (1 - %s of the responsible box, weighted by [yolo2_hparam] coords = %g)' % (
             session.box_loss, {'iou': 'IoU', 'giou': 'GIoU', 'diou': 'DIoU', 'ciou': 'CIoU'}[session.box_loss], builder.hparam['coords']))
@@ -247,6 +303,8 @@ def main():
         logging.warning(describe_loss_options(session.loss_options))
     logging.warning('optimizer=%s, dtype=%s, world=%d, parameters=%d%s' % (args.optimizer, dtype, world, session.engine.n_params,
                                                                           ', ema_decay=%g' % session.ema_decay if session.ema is not None else ''))
+    if session.teacher is not None:
+        logging.warning('distillation: %s' % ', '.join('%s=%s' % (k, session.distill[k]) for k in distillation.KERNEL_KEYS))
     if accum_steps > 1 or weight_decay > 0:
         logging.warning('accum_steps=%d: effective batch %d (batch %d x accum_steps %d x world %d)%s' % (
             accum_steps, args.batch_size * accum_steps * world, args.batch_size, accum_steps, world,
@@ -363,6 +421,9 @@ def main():
                 writer.flush()
                 logging.warning('step %d: total_loss=%.6f iou_best=%.6f iou_normal=%.6f coords=%.6f prob=%.6f (%.1f img/s)'
                                 % (session.global_step, s['total_loss'], s['iou_best'], s['iou_normal'], s['coords'], s['prob'], rate))
+                if 'distill' in s:
+                    logging.warning('step %d: distill=%.6f distill_objectness=%.6f distill_coords=%.6f distill_prob=%.6f'
+                                    % (session.global_step, s['distill'], s['distill_objectness'], s['distill_coords'], s['distill_prob']))
             (bad,) = agree([not np.isfinite(s['total_loss'])], device)
             if bad:
                 raise FloatingPointError('total_loss is not finite (on at least one rank)')

@@ -16,6 +16,7 @@ I8_OUT_I8, I8_OUT_BF16, I8_OUT_F32, I8_OUT_ACC = 0, 1, 2, 3      # out_kind of y
 NMS_METHODS = {'hard': 0, 'linear': 1, 'gaussian': 2}               # YOLO2_NMS_*: method of yolo2_soft_nms
 BOX_LOSSES = {'mse': 0, 'iou': 1, 'giou': 2, 'diou': 3, 'ciou': 4}   # box_loss of yolo2_loss_box / yolo2_loss_box_partials
 CLASS_LOSSES = {'mse': 0, 'ce': 1, 'focal': 2}                        # class_loss of yolo2_loss_options
+DISTILL_CLASS_TERMS = {'mse': 0, 'kl': 1}                             # class_term of yolo2_distill_options
 
 
 class HipKernelError(RuntimeError):
@@ -26,6 +27,12 @@ class LossOptions(ctypes.Structure):
     """yolo2_loss_options of include/yolo2_hip.h (yolo2_loss_ex, yolo2_loss_ex_partials)."""
     _fields_ = [('size', ctypes.c_int), ('box_loss', ctypes.c_int), ('class_loss', ctypes.c_int), ('rescore', ctypes.c_int),
                 ('ignore_thresh', ctypes.c_float), ('label_smoothing', ctypes.c_float), ('focal_gamma', ctypes.c_float)]
+
+
+class DistillOptions(ctypes.Structure):
+    """yolo2_distill_options of include/yolo2_hip.h (yolo2_distill_partials)."""
+    _fields_ = [('size', ctypes.c_int), ('class_term', ctypes.c_int), ('scale_by_objectness', ctypes.c_int), ('weight', ctypes.c_float),
+                ('w_objectness', ctypes.c_float), ('w_coords', ctypes.c_float), ('w_prob', ctypes.c_float), ('temperature', ctypes.c_float)]
 
 
 _p = ctypes.c_void_p
@@ -90,6 +97,8 @@ SIGNATURES = {
     'yolo2_loss_box_partials': [_p, _i, _p, _p, _p, _p, _p, _p, _p, ctypes.POINTER(_f), _p, _p, _i, _i, _i, _i, _i, _i, _p, _i],
     'yolo2_loss_ex': [_p, _i, _p, _p, _p, _p, _p, _p, _p, ctypes.POINTER(_f), _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, ctypes.POINTER(LossOptions)],
     'yolo2_loss_ex_partials': [_p, _i, _p, _p, _p, _p, _p, _p, _p, ctypes.POINTER(_f), _p, _p, _i, _i, _i, _i, _i, _i, _p, ctypes.POINTER(LossOptions)],
+    'yolo2_distill_partials': [_p, _i, _i, _p, _i, _i, _p, _p, _i, _i, _i, _i, _i, _p, ctypes.POINTER(DistillOptions)],
+    'yolo2_distill_objectives': [_p, _p, _i, _i, _i, _i, _p],
     'yolo1_loss': [_p, _i, _p, _p, _p, _p, _p, _p, ctypes.POINTER(_f), _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
     'yolo1_head_decode': [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
     'yolo2_leaky_bwd': [_p, _p, _p, _l, _f, _i, _p],
@@ -168,6 +177,7 @@ QUERIES = {
     'yolo2_bias_grad_workspace_bytes': (ctypes.c_size_t, [_i]),
     'yolo2_image_prep_workspace_bytes': (ctypes.c_size_t, [_i]),
     'yolo2_loss_workspace_bytes': (ctypes.c_size_t, [_i, _i, _i]),
+    'yolo2_distill_workspace_bytes': (ctypes.c_size_t, [_i, _i, _i]),
     'yolo2_nms_workspace_bytes': (ctypes.c_size_t, [_i, _i, _i]),
     'yolo2_wbf_workspace_bytes': (ctypes.c_size_t, [_i, _i, _i]),
     'yolo2_clip_workspace_bytes': (ctypes.c_size_t, [_i]),

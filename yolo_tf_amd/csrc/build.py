@@ -27,6 +27,7 @@ SOURCES = {
     'layout.hip': [],
     'optim.hip': [],
     'head.hip': ['-ffp-contract=off'],
+    'distill.hip': ['-ffp-contract=off'],
     'yolo1.hip': ['-ffp-contract=off'],
     'nms.hip': ['-ffp-contract=off'],
     'soft_nms.hip': ['-ffp-contract=off'],

@@ -9,10 +9,9 @@
 // The four objective sums are reduced wave -> block -> a deterministic second pass.
 #include "common.h"
 #pragma clang fp contract(off)
+#include "head_math.h"
 #include "box_loss.h"
 #include "loss_opts.h"
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // MODE (box_loss.h): Y2_BOX_MSE regresses the responsible anchor's box with the reference's squared error on (sx, sy, sqrt w, sqrt h); the
 // other modes put 1 - q of an IoU-family score in the `coords` slot and its closed-form gradient in channels 1..4, on the responsible lanes

@@ -389,6 +389,46 @@ def loss_ws_floats(B, cells, A):
     return workspace_bytes('loss', B, cells, A) // 4
 
 
+def distill_options(weight=1.0, objectness=1.0, coords=1.0, prob=1.0, class_term='mse', temperature=1.0, scale_by_objectness=True):
+    """The ``_lib.DistillOptions`` of yolo2_distill_partials, checked on the host: an unknown class term, a temperature
+    that is not positive and finite, a negative or non-finite weight raise ValueError naming the option."""
+    try:
+        term = _lib.DISTILL_CLASS_TERMS[class_term]
+    except (KeyError, TypeError):
+        raise ValueError('class_term = %r: one of %s' % (class_term, ', '.join(_lib.DISTILL_CLASS_TERMS)))
+    try:
+        T = float(temperature)
+        w = [float(v) for v in (weight, objectness, coords, prob)]
+    except (TypeError, ValueError):
+        raise ValueError('temperature and the distill weights are numbers, not %r, %r' % (temperature, (weight, objectness, coords, prob)))
+    if not 0.0 < T < float('inf'):
+        raise ValueError('temperature = %r: positive and finite' % (temperature,))
+    for name, v in zip(('weight', 'objectness', 'coords', 'prob'), w):
+        if not 0.0 <= v < float('inf'):
+            raise ValueError('%s = %r: a weight >= 0' % (name, v))
+    if scale_by_objectness not in (False, True, 0, 1):
+        raise ValueError('scale_by_objectness = %r: True or False' % (scale_by_objectness,))
+    return _lib.DistillOptions(ctypes.sizeof(_lib.DistillOptions), term, int(bool(scale_by_objectness)), w[0], w[1], w[2], w[3], T)
+
+
+def distill_partials(student, ld_s, teacher, ld_t, dlogits, ws, B, ch, cw, A, C, **options):
+    """The distill kernel alone: adds d(weighted distill term)/d student into ``dlogits`` (the student's dtype and ld; None: objectives only) and
+    leaves per-workgroup partial sums in ``ws``; ``distill_objectives`` reduces them on demand.  ``student`` / ``teacher``: f32 or bf16 logits,
+    each with its own ld; the two dtypes may differ.  Options as in ``distill_options``."""
+    opt = distill_options(**options)
+    call('yolo2_distill_partials', ptr(student), ld_s, dtype_code(student.dtype), ptr(teacher), ld_t, dtype_code(teacher.dtype), ptr(dlogits), ptr(ws),
+         B, ch, cw, A, C, _stream(), ctypes.byref(opt))
+
+
+def distill_objectives(ws, objectives, B, ch, cw, A):
+    """objectives f32[3]: the unweighted objectness, coords and prob terms of the last ``distill_partials`` on ``ws``."""
+    call('yolo2_distill_objectives', ptr(ws), ptr(objectives), B, ch, cw, A, _stream())
+
+
+def distill_ws_floats(B, cells, A):
+    return workspace_bytes('distill', B, cells, A) // 4
+
+
 def nms(conf, xy_min, xy_max, order, ws, B, N, C, thr, thr_iou):
     call('yolo2_nms', ptr(conf), ptr(xy_min), ptr(xy_max), ptr(order), ptr(ws), B, N, C, thr, thr_iou, _stream())
 
@@ -498,7 +538,7 @@ def bn_fold(W, gamma, beta, mean, var, Wf, bias, rows, C, eps):
 
 
 def workspace_bytes(kind, *args):
-    """Caller-owned scratch size of an entry family: 'conv2d', 'bn', 'bias_grad', 'image_prep', 'loss', 'nms', 'wbf', 'clip', 'augment'
+    """Caller-owned scratch size of an entry family: 'conv2d', 'bn', 'bias_grad', 'image_prep', 'loss', 'distill', 'nms', 'wbf', 'clip', 'augment'
     (include/yolo2_hip.h yolo2_*_workspace_bytes)."""
     return int(_lib.query('yolo2_%s_workspace_bytes' % kind, *args))
 

@@ -6,6 +6,7 @@ import os
 import numpy as np
 import torch
 
+from . import distill as _distill
 from . import ops, options
 from .engine import Engine, layer_end_offsets, staggered
 from .graph import pad8
@@ -144,7 +145,7 @@ class TrainSession(object):
                  config=None, seed=0, world_size=1, bucket_mb=64.0, preprocess_mode=0, sizes=None, grad_dtype='f32', comm_cus=None, comm_timing=False,
                  sync_bn=False, shard_optimizer=False, deterministic=None, ema_decay=None, box_loss=None,
                  class_loss=None, ignore_thresh=None, rescore=None, label_smoothing=None, focal_gamma=None,
-                 accum_steps=None, weight_decay=None, weight_decay_mode=None):
+                 accum_steps=None, weight_decay=None, weight_decay_mode=None, teacher=None, distill=None):
         """``sizes``: optional list of (width, height) input sizes for multi-scale training (BASELINE configs[3]); buffers are
         allocated once for the largest, ``set_size`` switches between them, the builder's configured size is selected first.
 
@@ -166,7 +167,14 @@ class TrainSession(object):
         loss and backward and add their gradient into a second arena, the K-th forms the mean and updates; ``micro_step`` counts 0 .. K - 1, ``global_step``
         counts updates.  ``weight_decay`` with ``weight_decay_mode`` 'l2' (wd * w joins the gradient of the filters before the collective, the clip and the
         optimizer) or 'decoupled' (AdamW: the filters are scaled by 1 - lr * wd ahead of the update).  None (default): the ``[mi355x]`` key of the same
-        name; absent, 1 and 0: off -- nothing is allocated, no launch is added."""
+        name; absent, 1 and 0: off -- nothing is allocated, no launch is added.
+
+        ``teacher``: a ``DetectSession`` of a YOLOv2 network with this one's anchors, classes and grids, restored by the caller, for objectness-scaled
+        distillation: every ``forward_backward`` runs the teacher's forward on the same images and adds the gradient of the weighted
+        distill term into the logit gradient, behind the loss.  With ``sizes`` the teacher is built with the same sizes; ``set_size`` switches both.
+        ``distill``: a dict of the ``[distill]`` keys weight, objectness, coords, prob, class_term, temperature, scale_by_objectness
+        (yolo_tf_amd/distill.py); a key it lacks, or None, is read from the config's section, else its default.  ``teacher`` None or weight 0: off --
+        ``session.teacher`` is None, nothing is allocated or launched."""
         assert builder.training, 'call builder(data, training=True) first'
         cfg = config if config is not None else getattr(builder, 'config', None)         # the one config every option below is read from
         self.accum_steps, self.weight_decay, self.weight_decay_mode = recipe_options(cfg, accum_steps, weight_decay, weight_decay_mode)
@@ -194,6 +202,13 @@ class TrainSession(object):
                 traced[wh] = builder.trace(wh[0], wh[1], training=True)
         largest = max(traced, key=lambda wh: wh[0] * wh[1])
         assert all(w <= largest[0] and h <= largest[1] for w, h in traced), 'one size must contain all the others'
+        self.teacher, self.distill = None, None
+        if teacher is not None:
+            resolved = _distill.options(cfg, **(distill or {}))
+            if resolved['weight'] > 0:
+                _distill.refuse_pair(_distill.head({wh: gm[1] for wh, gm in traced.items()}, self.v1, batch_size),
+                                     _distill.head(teacher.models, teacher.v1, teacher.B, int8=getattr(teacher, 'dtype', None) == 'int8'))
+                self.teacher, self.distill = teacher, _distill.kernel_options(resolved)
         if deterministic is None:
             deterministic = options.read(cfg, 'deterministic') or os.environ.get('YOLO2_DETERMINISTIC', '0') == '1'
         self.deterministic = bool(deterministic)
@@ -223,6 +238,13 @@ class TrainSession(object):
         for wh, (g, _) in traced.items():
             if wh != largest:
                 e.add_size(g)
+        if self.teacher is not None:
+            # three partial sums per workgroup and the three reduced terms; a teacher session that holds more images than this one reads them from a
+            # buffer of its own size whose first B images are the batch (its moving-average BN keeps the images independent)
+            self.distill_ws = torch.zeros(ops.distill_ws_floats(batch_size, m0.cells, self.A), dtype=torch.float32, device=dev)
+            self.distill_dev = torch.zeros(3, dtype=torch.float32, device=dev)
+            self._teacher_images = torch.zeros(self.teacher.B * largest[0] * largest[1] * 3, dtype=torch.float32, device=dev) if self.teacher.B > batch_size else None
+            self._distill_pending = None
         self.size = None
         self.set_size(*own)
         self.hparam = [builder.hparam[k] for k in OBJECTIVE_KEYS]
@@ -289,6 +311,8 @@ class TrainSession(object):
         self.model = self.models[wh]
         self.labels = self._labels[wh]
         self.size = wh
+        if self.teacher is not None:
+            self.teacher.set_size(*wh)
 
     def upload_labels(self, labels):
         for dst, src in zip(self.labels, labels):
@@ -316,6 +340,8 @@ class TrainSession(object):
             ops.loss_partials(logits, ld, self.anchors, self.labels, self.hparam, dlogits, self.loss_ws, self.B, m.cell_height, m.cell_width, self.A, self.C,
                               **self.loss_options)
             self._objectives_pending = (m.cell_height, m.cell_width)
+            if self.teacher is not None:
+                self._distill(images, logits, ld, dlogits)
         if self._recipe:
             self._backward_recipe(defer_collectives)
         elif self.reducer is not None:
@@ -350,6 +376,20 @@ class TrainSession(object):
             self._early_pending = (alpha, hp['beta1'], hp['beta2'], hp['epsilon'])
         else:
             e.backward()
+
+    def _distill(self, images, logits, ld, dlogits):
+        """The teacher's forward on this batch, then the distill launch: d(weighted distill term)/d logits is added into ``dlogits``, which the loss has
+        just written, and the partial sums of the three terms stay in ``distill_ws`` until ``fetch`` asks.  Same stream: the launch runs behind both
+        forwards and ahead of the backward.  In deterministic mode the teacher's convolutions take the fixed-order routes too."""
+        m, t = self.model, self.teacher
+        if self._teacher_images is not None:
+            staged = self._teacher_images[:t.B * images[0].numel()]
+            staged[:images.numel()].copy_(images.reshape(-1))
+            images = staged
+        with ops.deterministic_launches(self.deterministic):
+            t_logits, t_ld = t.logits(images, self.preprocess_mode)
+        ops.distill_partials(logits, ld, t_logits, t_ld, dlogits, self.distill_ws, self.B, m.cell_height, m.cell_width, self.A, self.C, **self.distill)
+        self._distill_pending = (m.cell_height, m.cell_width)
 
     def _backward_recipe(self, defer_collectives):
         """Backward of micro-batch ``micro_step`` with gradient accumulation and / or weight decay on.  Micro-batches 0 .. K - 2 are
@@ -487,17 +527,26 @@ class TrainSession(object):
 
     def fetch(self):
         """Synchronises and returns {'total_loss', 'iou_best', 'iou_normal', 'coords', 'prob'} of the last step
-        (the five scalars the reference summarises, config.ini:63).  With ``accum_steps`` > 1 these are the objectives of the last MICRO-batch that ran,
+        (the five scalars the reference summarises, config.ini:63); with a teacher also 'distill_objectness', 'distill_coords', 'distill_prob' (the
+        unweighted terms) and 'distill' (their weighted sum), which then is part of 'total_loss'.  With ``accum_steps`` > 1 these are the objectives of the last MICRO-batch that ran,
         not a mean over the update's micro-batches."""
         if getattr(self, '_objectives_pending', None):
             ops.loss_objectives(self.loss_ws, self.objectives_dev, self.B, self._objectives_pending[0], self._objectives_pending[1], self.A)
             self._objectives_pending = None
+        if self.teacher is not None and self._distill_pending:
+            ops.distill_objectives(self.distill_ws, self.distill_dev, self.B, self._distill_pending[0], self._distill_pending[1], self.A)
+            self._distill_pending = None
         ops.check_async_errors()           # device-detected failures (a stream-K hand-off that gave up) become exceptions here
         vals = self.objectives_dev.cpu().numpy().astype(np.float64)
         out = {k: float(v) for k, v in zip(OBJECTIVE_KEYS, vals)}
         out['regularization'] = float(self.engine.reg_loss.item())        # slim.l2_regularizer terms (YOLO v1 fully connected layers; 0 for yolo2)
         out['total_loss'] = float(sum(v * w for v, w in zip(vals, self.hparam))) + out['regularization']
         self.builder.objectives.update({k: out[k] for k in OBJECTIVE_KEYS})
+        if self.teacher is not None:
+            d, o = self.distill_dev.cpu().numpy().astype(np.float64), self.distill
+            out.update(zip(_distill.SCALARS[:3], (float(v) for v in d)))
+            out['distill'] = float(o['weight'] * (o['objectness'] * d[0] + o['coords'] * d[1] + o['prob'] * d[2]))
+            out['total_loss'] += out['distill']
         return out
 
 
@@ -518,6 +567,7 @@ class DetectSession(object):
         an image can need up to M * C rows ('evaluation' asks for ``tta.evaluation_rows(M, C)``); too few is reported by ``tta_check``, never silently cut."""
         assert not builder.training
         self.builder = builder
+        self.dtype = dtype
         self.v1 = getattr(builder, 'family', 'yolo2') == 'yolo'
         own = (builder.width, builder.height)
         traced = {own: (builder.graph, builder.model)}
@@ -699,6 +749,15 @@ class DetectSession(object):
             self.async_errors.raise_if_pending()
             self.async_errors.snapshot()
         return self.conf, self.xy_min, self.xy_max
+
+    def logits(self, images, preprocess_mode=0):
+        """``set_images`` plus ``forward``, with no decode and no NMS and no synchronisation: the output tensor [B, cells, ld] (the engine's buffer, in
+        its dtype) and its ``ld``.  What a TrainSession reads of its teacher."""
+        e = self.engine
+        e.set_images(images, preprocess_mode)
+        e.forward()
+        self._attrs_valid = False
+        return e.act[e.output()]
 
     def attrs(self):
         """iou [B,N], prob [B,N,C], xy, wh [B,N,2] of the last run (model/yolo2/__init__.py:36-56), decoded on first use."""

@@ -222,9 +222,12 @@ class FileWriter(object):
         self._write(encode_event(time.time() if wall_time is None else wall_time, step=step, images=list(images)))
 
     def add_training_summary(self, step, fetched):
-        """The five scalars of the reference's [summary] section from TrainSession.fetch()'s dict."""
+        """The five scalars of the reference's [summary] section from TrainSession.fetch()'s dict; with a teacher also the
+        weighted distill term and its three unweighted parts."""
+        distill = [('total_loss/distill', fetched['distill'])] + [('total_loss/distill/' + k, fetched['distill_' + k]) for k in ('objectness', 'coords', 'prob')] \
+            if 'distill' in fetched else []
         self.add_scalars(step, [('total_loss', fetched['total_loss'])] +
-                         [('total_loss/objectives/' + k, fetched[k]) for k in ('iou_best', 'iou_normal', 'coords', 'prob')])
+                         [('total_loss/objectives/' + k, fetched[k]) for k in ('iou_best', 'iou_normal', 'coords', 'prob')] + distill)
 
     def flush(self):
         self._f.flush()
