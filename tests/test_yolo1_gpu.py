@@ -21,8 +21,9 @@ def make_builder(names, size, training, basedir):
     from yolo_tf_amd.model import yolo
     cfg = utils.make_config([os.path.join(ROOT, 'config.ini'), os.path.join(ROOT, 'config', 'yolo', 'tiny-%d.ini' % names)], basedir)
     cfg.set('cache', 'names', os.path.join(ROOT, cfg.get('cache', 'names')))
-    cfg.set('yolo', 'width', str(size))
-    cfg.set('yolo', 'height', str(size))
+    width, height = size if isinstance(size, tuple) else (size, size)
+    cfg.set('yolo', 'width', str(width))
+    cfg.set('yolo', 'height', str(height))
     utils.ensure_names(cfg)
     b = yolo.Builder(None, cfg)
     b(None, training=training)
@@ -45,27 +46,40 @@ def strip(params, scope='yolo_tiny'):
     return {k[len(scope) + 1:]: v for k, v in params.items()}
 
 
-@pytest.mark.parametrize('dtype,B', [('f32', 2), ('bf16', 8)])
-def test_yolo1_train_step_matches_oracle(basedir, dtype, B):
+# B = 1: one real row in every fully connected layer's 128-row tile (how detect.py is normally used).  192 x 128: 3 x 2 cells -- the flatten order and
+# cell_width != cell_height matter.
+# The loss makes discrete choices (the responsible box is `iou == max iou`, d|x|/dx is a sign): where two boxes of an object cell tie at bf16 resolution
+# the device and the oracle may each be right with different boxes, and the gradients then differ by that cell's whole share -- a third of everything at
+# B = 1.  Seed 0 is such an input at B = 1: the bf16 and the f32 ORACLE disagree by 0.31 rel-L2 on fc/biases (the loss gradient itself) while the bf16 device
+# is within 0.002 of the f32 oracle (device vs bf16 oracle: 0.52 on conv1/biases, 0.31 on fc/biases).  A bf16 case therefore requires that both oracles make
+# the same choices -- a condition on the input alone -- and a seed that violates it is replaced (7: the oracles agree, the device is within 0.023 of the bf16
+# oracle on every parameter), never the tolerance.
+SEEDS = {('bf16', 1): 7}
+
+
+@pytest.mark.parametrize('dtype,B,size', [('f32', 2, 192), ('bf16', 8, 192), ('f32', 1, 192), ('bf16', 1, 192), ('f32', 2, (192, 128))],
+                         ids=['f32-2', 'bf16-8', 'f32-1', 'bf16-1', 'f32-2-192x128'])
+def test_yolo1_train_step_matches_oracle(basedir, dtype, B, size):
     from yolo_tf_amd.session import TrainSession
     from yolo_tf_amd.utils import data
-    classes, size, boxes = 20, 192, 2          # 192 / 64 = 3x3 cells: the fully connected head scales with the grid
+    classes, boxes = 20, 2                     # 192 / 64 = 3x3 cells: the fully connected head scales with the grid
+    width, height = size if isinstance(size, tuple) else (size, size)
+    cell_w, cell_h = width // 64, height // 64
     b = make_builder(classes, size, True, basedir)
     assert b.hparam == HP
     sess = TrainSession(b, B, dtype=dtype, optimizer='adam', learning_rate=1e-3, seed=2)
     e = sess.engine
     params0 = strip(e.get_variables())
-    rng = np.random.RandomState(0)
+    rng = np.random.RandomState(SEEDS.get((dtype, B), 0))
     for k in list(params0):
         if k.endswith('biases'):
             params0[k] = (rng.randn(*params0[k].shape) * 0.1).astype(np.float32)
     e.set_variables({'yolo_tiny/' + k: v for k, v in params0.items()})
-    cells = size // 64
-    spec = R.yolo1_tiny_spec(classes, boxes, cells * cells)
+    spec = R.yolo1_tiny_spec(classes, boxes, cell_h * cell_w)
     masks = {'dropout0': (rng.rand(B, 256) < 0.5).astype(np.uint8), 'dropout1': (rng.rand(B, 4096) < 0.5).astype(np.uint8)}
     e.dropout_masks = {'yolo_tiny/' + k: torch.from_numpy(v.reshape(-1)).cuda() for k, v in masks.items()}
-    images = rng.uniform(0, 255, (B, size, size, 3)).astype(np.float32)
-    labels = data.synthetic_batch(B, classes, cells, cells, seed=5)
+    images = rng.uniform(0, 255, (B, height, width, 3)).astype(np.float32)
+    labels = data.synthetic_batch(B, classes, cell_w, cell_h, seed=5)
     sess.upload_labels(labels)
     sess.forward_backward(torch.from_numpy(images).cuda())
     got = sess.fetch()
@@ -78,8 +92,13 @@ def test_yolo1_train_step_matches_oracle(basedir, dtype, B):
     q = None if f32 else R.bf16_round
     x = np.stack([R.per_image_standardization(i) for i in images]).astype(np.float32)
     net_ref, caches = R.yolo1_forward(spec, params0, x, masks, quant=q)
-    m = R.yolo1_model_decode(net_ref, classes, boxes, cells, cells, training=True)
+    m = R.yolo1_model_decode(net_ref, classes, boxes, cell_h, cell_w, training=True)
     obj, aux = R.yolo1_objectives(m, labels)
+    if not f32:      # the input's own condition: the f32 oracle picks the same responsible boxes and sees the same signs under them
+        m32 = R.yolo1_model_decode(R.yolo1_forward(spec, params0, x, masks)[0], classes, boxes, cell_h, cell_w, training=True)
+        best = aux['mask_best'] > 0
+        assert np.array_equal(R.yolo1_objectives(m32, labels)[1]['mask_best'] > 0, best), 'two boxes of an object cell tie at bf16 resolution: replace the seed'
+        assert np.array_equal(np.sign(m32['wh01_sqrt_base'])[best], np.sign(m['wh01_sqrt_base'])[best]), 'a responsible box has a side within bf16 resolution of 0'
     loss = float(sum(float(obj[k]) * HP[k] for k in R.OBJECTIVE_KEYS))
     dnet = R.yolo1_loss_backward(m, labels, aux, HP, classes, boxes, width)
     gref, reg = R.yolo1_backward(spec, params0, caches, dnet, quant=q)
@@ -100,28 +119,33 @@ def test_yolo1_train_step_matches_oracle(basedir, dtype, B):
     assert sess.global_step == 1 and torch.isfinite(e.params).all()
 
 
-def test_yolo1_detect_matches_oracle(basedir):
+@pytest.mark.parametrize('dtype,B,size', [('f32', 1, 192), ('f32', 2, 192), ('bf16', 1, 192), ('bf16', 2, 192), ('f32', 2, (192, 128))],
+                         ids=['f32-1', 'f32-2', 'bf16-1', 'bf16-2', 'f32-2-192x128'])
+def test_yolo1_detect_matches_oracle(basedir, dtype, B, size):
     from yolo_tf_amd.session import DetectSession
-    classes, size, boxes, B = 20, 192, 2, 2
+    classes, boxes = 20, 2
+    width, height = size if isinstance(size, tuple) else (size, size)
+    cell_w, cell_h = width // 64, height // 64
+    tol = 1e-4 if dtype == 'f32' else 3e-2       # bf16: the oracle on bf16-rounded weights and activations, the train-step test's tolerance for `net`
     b = make_builder(classes, size, False, basedir)
-    sess = DetectSession(b, B, dtype='f32', seed=3)
+    sess = DetectSession(b, B, dtype=dtype, seed=3)
     params = strip(sess.engine.get_variables())
     rng = np.random.RandomState(1)
     for k in list(params):
         if k.endswith('biases'):
             params[k] = (rng.randn(*params[k].shape) * 0.1).astype(np.float32)
     sess.engine.set_variables({'yolo_tiny/' + k: v for k, v in params.items()})
-    images = rng.uniform(0, 255, (B, size, size, 3)).astype(np.float32)
+    images = rng.uniform(0, 255, (B, height, width, 3)).astype(np.float32)
     conf, mn, mx = [t.clone() for t in sess.run(torch.from_numpy(images).cuda())]
-    cells = size // 64
     x = np.stack([R.per_image_standardization(i) for i in images]).astype(np.float32)
-    net, _ = R.yolo1_forward(R.yolo1_tiny_spec(classes, boxes, cells * cells), params, x, None)
-    m = R.yolo1_model_decode(net, classes, boxes, cells, cells, training=False)
-    n = cells * cells
-    assert rel(conf.cpu().numpy().reshape(B, n, boxes, classes), m['conf']) <= 1e-4
-    assert rel(mn.cpu().numpy().reshape(B, n, boxes, 2), m['xy_min']) <= 1e-4
-    assert rel(mx.cpu().numpy().reshape(B, n, boxes, 2), m['xy_max']) <= 1e-4
-    assert rel(b.model.conf.cpu().numpy(), m['conf']) <= 1e-4 and b.model.xy_min.shape == (B, n, boxes, 2)
+    net, _ = R.yolo1_forward(R.yolo1_tiny_spec(classes, boxes, cell_h * cell_w), params, x, None, quant=None if dtype == 'f32' else R.bf16_round)
+    m = R.yolo1_model_decode(net, classes, boxes, cell_h, cell_w, training=False)
+    n = cell_h * cell_w
+    got = [rel(conf.cpu().numpy().reshape(B, n, boxes, classes), m['conf']), rel(mn.cpu().numpy().reshape(B, n, boxes, 2), m['xy_min']),
+           rel(mx.cpu().numpy().reshape(B, n, boxes, 2), m['xy_max'])]
+    print('yolo1 detect %s B=%d %dx%d: conf / xy_min / xy_max rel %.2e %.2e %.2e (bound %.0e)' % ((dtype, B, width, height) + tuple(got) + (tol,)))
+    assert max(got) <= tol, got
+    assert rel(b.model.conf.cpu().numpy(), m['conf']) <= tol and b.model.xy_min.shape == (B, n, boxes, 2)
     # on-GPU NMS on these scores == the C oracle, bit for bit (the reference's detect.py path is model-family agnostic)
     thr = float(np.percentile(conf.cpu().numpy(), 80))
     order = sess.nms(thr, 0.4).cpu().numpy()

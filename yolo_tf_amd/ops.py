@@ -30,13 +30,19 @@ def conv2d(P, F, bias, O, B, H, W, Cp, ldp, Nf, ldo, ksize):
     call('yolo2_conv2d', ptr(P), ptr(F), ptr(bias), ptr(O), B, H, W, Cp, ldp, Nf, ldo, ksize, dtype_code(P.dtype), _stream())
 
 
+def _ws_bytes(ws):
+    return 0 if ws is None else ws.numel() * ws.element_size()
+
+
 def conv2d_ws(P, F, bias, O, ws, B, H, W, Cp, ldp, Nf, ldo, ksize):
-    call('yolo2_conv2d_ws', ptr(P), ptr(F), ptr(bias), ptr(O), ptr(ws), ws.numel() * ws.element_size(), B, H, W, Cp, ldp, Nf, ldo, ksize,
+    """``ws``: f32 tensor, or None -- the launch rule then only names kernels that need no workspace (as ``conv2d``)."""
+    call('yolo2_conv2d_ws', ptr(P), ptr(F), ptr(bias), ptr(O), ptr(ws), _ws_bytes(ws), B, H, W, Cp, ldp, Nf, ldo, ksize,
          dtype_code(P.dtype), _stream())
 
 
 def conv2d_bias_leaky(P, F, bias, O, ws, B, H, W, Cp, ldp, Nf, ldo, ksize, alpha):
-    call('yolo2_conv2d_bias_leaky', ptr(P), ptr(F), ptr(bias), ptr(O), ptr(ws), ws.numel() * ws.element_size(), B, H, W, Cp, ldp, Nf, ldo, ksize,
+    """``ws``: as for ``conv2d_ws``."""
+    call('yolo2_conv2d_bias_leaky', ptr(P), ptr(F), ptr(bias), ptr(O), ptr(ws), _ws_bytes(ws), B, H, W, Cp, ldp, Nf, ldo, ksize,
          alpha, dtype_code(P.dtype), _stream())
 
 
